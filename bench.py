@@ -16,6 +16,12 @@ over the config's 100 pairs:  value = pairs / (t_steps + t_setup * pairs/100).
 
 N > 1 (weak scaling): every rank holds the full matrix + hierarchy (the path shards by independent pairs,
 SURVEY.md 8e), solves its own K batches, and the resistances are gathered with one RCCL all_gather.
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the line. `--full` adds everything
+else the line used to carry: the CPU baseline and the parity figures against the tight oracle (--cpu-sample), the other
+preconditioner precision (--compare-steps), the extra legs (--extra-legs), the host-CSR set-up (--host-csr), the live PMC
+passes (--pmc-live), the 100-pair job and the K = 1 SpMV figure. Each of those options, given explicitly, also works
+without --full. `--dump-outputs DIR` writes what the timed path returned for its last step as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -315,6 +321,23 @@ def cpu_baseline_entry(cb, n_full, size, sample_size):
         entry["_tight"] = {"R": cb["tight_R"], "pairs": cb["tight_pairs"], "max_true_relres": cb["tight_max_true_relres"],
                            "wall_s": cb["tight_wall_s"]}
     return entry
+
+
+DUMP_SAMPLE = 4 * 1024 * 1024   # entries kept of an output array larger than this (a fixed, seeded sample)
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (float32 when the path computed in float32). An array of
+    more than DUMP_SAMPLE entries is stored as a fixed sample (rng(0), sorted indices in DIR/<name>_index.npy)."""
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=DUMP_SAMPLE, replace=False))
+            np.save(os.path.join(d, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def run_pairs(h, batch_pairs, K, Wm, sync=None, first_batch=0, one_call=True):
@@ -775,7 +798,13 @@ def main():
                          "hands over a component's pair list, and the library streams them through its columns; per-step: "
                          "one call per batch (every batch at the pace of its slowest column)")
     ap.add_argument("--precision", default="double", choices=["double", "single"])
-    ap.add_argument("--cpu-sample", type=int, default=3000, help="raster edge of the CPU-baseline / parity sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="run everything beside the headline (see the options below that name it); off: set-up, warm-up, "
+                         "the timed steps and the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned for its last step as DIR/<name>.npy")
+    ap.add_argument("--cpu-sample", type=int, default=None,
+                    help="raster edge of the CPU-baseline / parity sample (0 = skip; default 3000 with --full, else 0)")
     ap.add_argument("--criterion", type=int, default=0)
     ap.add_argument("--precond", default="same", choices=["same", "fp32"],
                     help="precision of the AMG preconditioner (hierarchy, V-cycle, stored search direction) of the path "
@@ -786,31 +815,32 @@ def main():
                     help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI; gloo only to exercise the "
                          "multi-rank code path on a box with fewer GPUs than ranks)")
     ap.add_argument("--opt", action="append", default=[], help="extra csgpu_opts override key=value (tuning)")
-    ap.add_argument("--compare-steps", type=int, default=-1,
+    ap.add_argument("--compare-steps", type=int, default=None,
                     help="N=1 only: also time this many steps on the OTHER preconditioner precision (see --precond) and "
                          "report them as value_mixed / value_fp64 with their own roofline; -1 = the same number as "
-                         "--steps, 0 = skip")
+                         "--steps, 0 = skip (default -1 with --full, else 0)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak (default, what the driver runs): every rank solves --steps batches. strong: the config's "
                          "FIXED pair list (--pairs, default 100 = BASELINE configs[2]) is dealt over the ranks at pair "
                          "granularity; --steps is ignored and the line reports the whole job incl. the per-rank setup")
     ap.add_argument("--pairs", type=int, default=100, help="--scaling strong: total number of pairs of the job")
-    ap.add_argument("--host-csr", type=int, default=1,
+    ap.add_argument("--host-csr", type=int, default=None,
                     help="N=1 only: also time csgpu_setup from host CSR arrays the way Julia hands them (Int64, 1-based) "
                          "at the bench size and report setup_host_csr_s (needs ~30 GB of host memory and ~20 s at "
-                         "10000^2; 0 = skip)")
-    ap.add_argument("--extra-legs", type=int, default=1,
+                         "10000^2; 0 = skip; default 1 with --full, else 0)")
+    ap.add_argument("--extra-legs", type=int, default=None,
                     help="N=1 only: also report value_shortcut (K-1 anchor solves + focal-voltage gather -> all K(K-1)/2 "
                          "resistances, SURVEY.md 8d) and value_with_voltages (whole solution vector carried, explicit 1e-4 "
-                         "check); 0 = skip")
+                         "check), the nodata15 / config3_fp32 / config4_network / network_geometric legs; 0 = skip "
+                         "(default 1 with --full, else 0)")
     ap.add_argument("--cpu-baseline-only", type=int, default=0, metavar="N_FULL",
                     help="internal: run only the CPU-baseline leg on a --cpu-sample raster, scale to N_FULL nodes, print "
                          "its JSON object and exit (the bench runs this in a child process so that nothing on the host "
                          "side can take the GPU line down)")
-    ap.add_argument("--pmc-live", type=int, default=1,
+    ap.add_argument("--pmc-live", type=int, default=None,
                     help="N=1 only: measure roofline.traffic in this run with two rocprofv3 --pmc passes over a one-batch child "
                          "process (~1 min); 0 = report the committed PMC pass of profiles/pmc_traffic.json when its kernel-source "
-                         "hash matches this build")
+                         "hash matches this build (default 1 with --full, else 0)")
     ap.add_argument("--cpu-legs", default="", help="internal (CPU child): comma list of nodata,fp32,geometric")
     ap.add_argument("--leg-sample", type=int, default=2000,
                     help="raster edge of the samples on which the nodata15 / config3_fp32 legs are compared with the tight oracle")
@@ -826,6 +856,9 @@ def main():
     ap.add_argument("--cpu-full-only", type=int, default=0, help="internal (CPU child): measure the oracle at --size")
     ap.add_argument("--cpu-full-threads", type=int, default=16)
     args = ap.parse_args()
+    for name, full_default in (("cpu_sample", 3000), ("compare_steps", -1), ("extra_legs", 1), ("host_csr", 1), ("pmc_live", 1)):
+        if getattr(args, name) is None:
+            setattr(args, name, full_default if args.full else 0)
     if args.cpu_full_only > 0:
         print(json.dumps(cpu_full_size_measure(args.size, args.cpu_full_threads, args.precision == "single")), flush=True)
         return
@@ -916,6 +949,9 @@ def main():
     # untimed warm-up of the setup path on a small raster (first launch of every kernel loads its code object; a fresh
     # process pays ~1 s for that once -- the solve path is warmed by the --warmup batches below)
     other = {"same": "fp32", "fp32": "same"}[args.precond] if vb == 8 else None
+    csteps = K if args.compare_steps < 0 else args.compare_steps
+    compare = world == 1 and csteps > 0 and other is not None      # the other precision is timed too (--full)
+    # (both precisions are warmed up in every run: the process then reaches the timed set-up in the same state either way)
     for precond in ((args.precond, other) if other else (args.precond,)):
         wn = min(768, size)
         hw = lib.raster_setup(np.ascontiguousarray(g[:wn, :wn]), make_opts(precond))
@@ -947,6 +983,10 @@ def main():
     t_gather = time.perf_counter() - t1
     elapsed_rank = elapsed + t_gather
     elapsed = elapsed_rank
+    if args.dump_outputs and rank == 0:
+        # the resistances of the last timed step (every rank's, gathered, when N > 1)
+        last = results[-1] if dist is None else torch.cat([t_.cpu() for t_ in gathered]).numpy().reshape(world, K, B)[:, -1, :]
+        dump_outputs(args.dump_outputs, {"resistances": last})
     rank_reports = [rank_identity(torch, rank, dev_index, has_cuda, elapsed_rank / K * 1e3, K * B, agg)]
     multi = None
     if dist is not None:
@@ -1006,12 +1046,13 @@ def main():
         setup_s = (info["setup_ms"] + info["upload_ms"]) / 1e3
         # setup is per GPU and amortised over the config's 100 pairs per matrix
         value = pairs_done / (elapsed + setup_s * (K * B) / 100.0)
-        spmv1_ms = h.spmv_bench(1, 10)
         mixed = vb == 8 and info["precond_bytes"] == 4
         path_name = "mixed" if mixed else ("fp64" if vb == 8 else "fp32")
         roof = roofline_of(info, agg)
-        roof.update({"spmv_k1_avg_ms": spmv1_ms,
-                     "spmv_k1_GBs": info["spmv_bytes_fine"] / (spmv1_ms * 1e-3) / 1e9 if spmv1_ms > 0 else 0.0})
+        if args.full:   # a K = 1 SpMV timed on its own (10 launches)
+            spmv1_ms = h.spmv_bench(1, 10)
+            roof.update({"spmv_k1_avg_ms": spmv1_ms,
+                         "spmv_k1_GBs": info["spmv_bytes_fine"] / (spmv1_ms * 1e-3) / 1e9 if spmv1_ms > 0 else 0.0})
         tn_ = {8: "double", 4: "float"}
         roof["_prefix"] = "void csgpu::dia_cg_kernel<%s, %s, %d, 1>" % (tn_[vb], tn_[info["precond_bytes"] or vb], B)
         # the DOMINANT kernel is the one with the longest launch: since the residual update carries the restriction that is
@@ -1021,7 +1062,8 @@ def main():
         if roof_resid is not None and roof_resid["avg_ms"] > roof["avg_ms"]:
             roof_resid["dominant_by"] = "%.2f ms per launch against %.2f ms of the CG product, one launch each per iteration" % (
                 roof_resid["avg_ms"], roof["avg_ms"])
-            roof_resid.update({"spmv_k1_avg_ms": roof["spmv_k1_avg_ms"], "spmv_k1_GBs": roof["spmv_k1_GBs"]})
+            if "spmv_k1_avg_ms" in roof:
+                roof_resid.update({"spmv_k1_avg_ms": roof["spmv_k1_avg_ms"], "spmv_k1_GBs": roof["spmv_k1_GBs"]})
             roof = roof_resid
         out = {
             "metric": "pair-solves/sec (AMG-PCG, setup amortised over 100 pairs) on %dx%d raster pairwise" % (size, size),
@@ -1070,7 +1112,7 @@ def main():
             out["multi_gpu"] = multi
         else:
             out["rank0"] = rank_reports[0]
-        if world == 1:
+        if world == 1 and args.full:
             # BASELINE configs[2] AS A JOB: "100 focal pairs" = the first 100 pairs of the list handed
             # over in ONE csgpu_solve_pairs call on the handle just timed -- 32 + 32 + 32 + 4 at batch 32, the last batch at
             # the width its 4 columns ask for -- plus the set-up. `value` above amortises the set-up over 100 pairs at the
@@ -1102,8 +1144,7 @@ def main():
                 out["shortcut"] = {"failed": repr(e)}
         h.close()
         h = None
-        csteps = K if args.compare_steps < 0 else args.compare_steps
-        if world == 1 and csteps > 0 and other:
+        if compare:
             # the same workload, same warm-up and step count on the other preconditioner precision
             oname = "fp64" if other == "same" else "mixed"
             h2 = lib.raster_setup(g, make_opts(other))      # cold for the block sizes of this precision, see above
@@ -1400,6 +1441,8 @@ def strong_scaling(args, lib, torch, dist, dev, rank, world, make_opts, dtype, v
         h.close()
         if attempt == 0:
             job_cold_s = elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"resistances": full})    # the whole job is the timed step
     busy = [t_busy]
     setups = [t_setup]
     has_cuda = torch.cuda.is_available()
@@ -1498,6 +1541,11 @@ def network_workload(args, lib, torch, dist, dev, rank, world, sync):
     t_rank = time.perf_counter() - t0
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # the sources' voltages of every rank's last batch, and the cumulative node-current vector of the whole call
+        ends = [shard.pair_slice(K * B * world, r_, world)[1] for r_ in range(world)]
+        last = np.concatenate([v[max(e - B, 0):e] for e in ends])
+        dump_outputs(args.dump_outputs, {"source_voltages": last, "cum_current": cum})
     st = stats[0] if stats else {"total_iters": 0, "max_iters": 0, "max_relres": 0.0, "not_converged": 0, "device_ms": 0.0,
                                  "cg_spmv_ms": 0.0, "cg_spmv_calls": 0, "cg_spmv_bytes": 0, "batch": B}
     agg = {"total_iters": st["total_iters"], "max_relres": st["max_relres"], "not_converged": st["not_converged"]}

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_line_carries_the_nodata_leg(emu_lib):
     env = dict(os.environ, CSGPU_LIB=os.path.join(ROOT, "tests", "emu", "libcsgpu_emu.so"))
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "120", "--steps", "1", "--warmup", "1",
-                          "--batch", "8", "--cpu-sample", "0", "--precision", "single", "--host-csr", "0"],
+                          "--batch", "8", "--cpu-sample", "0", "--precision", "single", "--host-csr", "0", "--full"],
                          capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     line = json.loads(res.stdout.strip().splitlines()[-1])
@@ -38,7 +38,7 @@ def test_every_leg_of_the_fp64_line_carries_an_oracle_figure(emu_lib):
     env = dict(os.environ, CSGPU_LIB=os.path.join(ROOT, "tests", "emu", "libcsgpu_emu.so"))
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "120", "--steps", "1", "--warmup", "1",
                           "--batch", "8", "--cpu-sample", "90", "--leg-sample", "96", "--network-n", "4000", "--geometric-n",
-                          "4000", "--host-csr", "0"], capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
+                          "4000", "--host-csr", "0", "--full"], capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     line = json.loads(res.stdout.strip().splitlines()[-1])
     assert line["parity"]["ok"] and line["parity"]["max_rel_err_vs_oracle"] < 1e-6
@@ -56,3 +56,31 @@ def test_every_leg_of_the_fp64_line_carries_an_oracle_figure(emu_lib):
     assert line["config4_network"]["solve_device_s_all_sources"] > 0 and line["config4_network"]["cum_current_sum"] > 0
     assert line["nodata15"]["parity"]["lattice_period"] == 96
     assert set(line["leg_seconds"]) >= {"nodata15", "config3_fp32", "config4_network", "cpu_child", "leg_parity_gpu"}
+
+
+def test_plain_line_is_the_headline_and_dumps_the_last_step(emu_lib, tmp_path):
+    """Without --full the line carries the headline and none of the legs; --dump-outputs writes the resistances of the last
+    timed step (warm-up batch 0, timed batches 1 and 2 -> the pairs of batch 2), equal to a direct solve of those pairs."""
+    import numpy as np
+    import bench
+    env = dict(os.environ, CSGPU_LIB=os.path.join(ROOT, "tests", "emu", "libcsgpu_emu.so"))
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "120", "--steps", "2", "--warmup", "1",
+                          "--batch", "8", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=1500,
+                         env=env, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-2000:]
+    line = json.loads(res.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["unit"] == "pair-solves/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    for key in ("cpu_baseline", "parity", "nodata15", "config3_fp32", "config4_network", "network_geometric", "shortcut",
+                "with_voltages", "job_100_pairs", "value_mixed", "setup_host_csr_s"):
+        assert key not in line, key
+    assert "spmv_k1_avg_ms" not in line["roofline"] and not line["leg_seconds"]
+    R = np.load(str(tmp_path / "resistances.npy"))
+    assert R.dtype == np.float64 and R.shape == (8,)
+    _, pairs = bench.focal_pairs(120)
+    h = emu_lib.raster_setup(bench.make_raster(120), emu_lib.default_opts(device=0, batch=8))
+    try:
+        Rd, _, _, _ = h.solve_pairs([pairs[16 + c][0] for c in range(8)], [pairs[16 + c][1] for c in range(8)])
+    finally:
+        h.close()
+    assert np.max(np.abs(R - Rd) / np.abs(Rd)) < 1e-4
