@@ -1058,6 +1058,9 @@ struct SetupParams {
   // a 3 x 3 tile together; used when more than tile_split_min of the cells leave their tile because of it
   double tile_theta = default_tile_theta();
   double tile_split_min = default_tile_split_min();
+  // verdict of the expansion probe when the caller has run it already (csgpu.hip runs it before the locality reordering of a
+  // network, reorder.h: an expander is not reordered, and not probed twice): 0 = not run, 1 = expander, -1 = not one
+  int expander_verdict = 0;
 };
 
 // Q^T (with its traversal order) of the two-product form in CSR
@@ -1575,6 +1578,16 @@ inline void amg_setup_levels(Hierarchy<T>& H, const SetupParams& sp, const int* 
 template <class T>
 inline void lattice_level1_setup(Level<T>& L, const int* agg, int R, int C, int nagg, hipStream_t st);
 
+// The expansion probe's verdict on a large graph without coordinates (amg_setup_levels; csgpu.hip before a reordering)
+template <class T>
+inline bool expander_probe_says_expander(const Csr<T>& A, hipStream_t st) {
+  double mean_row = 0.0;
+  const double est = expansion_estimate(A, st, &mean_row);
+  if (knobs().verbose)
+    fprintf(stderr, "csgpu: expansion probe: mean row %.1f entries, estimated nnz(P) / nnz(A) after MIS(2) = %.2f\n", mean_row, est);
+  return est > 0.8 && mean_row >= 7.0;
+}
+
 // Build the hierarchy. A0 is moved into level 0. node_row/node_col (device, may be null) are raster coordinates.
 template <class T>
 inline void amg_setup(Hierarchy<T>& H, Csr<T>&& A0, const SetupParams& sp, const int* node_row, const int* node_col,
@@ -1659,11 +1672,7 @@ inline void amg_setup_levels(Hierarchy<T>& H, const SetupParams& sp, const int* 
     const bool cell_level = (sp.size0 || ts.unit_weights) && H.levels.size() == 1;
     if (knobs().expander_probe && H.levels.size() == 1 && !cur_row && !wts && sp.theta == 0.0 && n >= 100000) {
       // a large graph without coordinates: would the aggregation be thrown away? (expansion_probe_kernel)
-      double mean_row = 0.0;
-      const double est = expansion_estimate(L.A, st, &mean_row);
-      if (knobs().verbose)
-        fprintf(stderr, "csgpu: expansion probe: mean row %.1f entries, estimated nnz(P) / nnz(A) after MIS(2) = %.2f\n", mean_row, est);
-      if (est > 0.8 && mean_row >= 7.0) {
+      if (sp.expander_verdict != 0 ? sp.expander_verdict > 0 : expander_probe_says_expander(L.A, st)) {
         H.expander_probe_hit = true;
         L.weights.clear();
         L.omega = sp.omega_s / L.rho;

@@ -11,6 +11,7 @@
 #include "pcg.h"
 #include "raster.h"
 #include "lattice_setup.h"
+#include "reorder.h"
 
 namespace csgpu {
 
@@ -69,6 +70,7 @@ inline Knobs knobs_from_opts(const csgpu_opts& o) {
   k.tail_projection = flag(o.tail_projection, true);
   k.coarse_smoother = o.coarse_smoother;
   k.expander_probe = flag(o.expander_probe, true);
+  k.reorder = o.reorder > 0;
   k.nu_l1 = std::max(o.nu_l1, 0);
   k.nu_deep = std::max(o.nu_deep, 0);
   k.host_stream_block = std::max<int64_t>(o.host_stream_block, 0);
@@ -129,6 +131,7 @@ inline Knobs knobs_from_opts(const csgpu_opts& o) {
   if (on("NO_DEFLATION")) k.deflation = false;
   if (on("NO_TAIL_PROJECTION")) k.tail_projection = false;
   if (on("NO_EXPANDER_PROBE")) k.expander_probe = false;
+  num("REORDER", [&](double v) { k.reorder = v > 0; });
   if (on("COARSE_JACOBI")) k.coarse_smoother = 2;
   if (on("COARSE_CHEBYSHEV")) k.coarse_smoother = 1;
   num("NU_L1", [&](double v) { k.nu_l1 = (int)v; });
@@ -176,6 +179,7 @@ struct ISolver {
   virtual void spmv_host(const void* x, void* y, int k) = 0;
   virtual void raster_nodemap(int32_t* out, int64_t* rows, int64_t* cols) = 0;
   virtual int64_t components(int32_t* out) = 0;
+  virtual void get_permutation(int32_t* out) = 0;
   virtual void solve_raster(const void* source, void* curr_out, void* volt_out, csgpu_stats* stats) = 0;
   virtual void level_spmv_host(int lvl, int which, const void* x, void* y, int k, double* dots) = 0;
   virtual void get_level_matrix(int lvl, int which, int64_t* nrows, int64_t* ncols, int64_t* nnz, int32_t* rowptr,
@@ -304,6 +308,13 @@ struct Solver : ISolver {
   // the transfer operators and every Galerkin operator are those of the real graph. The C ABI keeps speaking the
   // reference's node numbering: ids and n-vectors are translated at the boundary (node2cell / cell2node).
   bool cellspace = false;
+  // Locality reordering of a network (csgpu_opts.reorder, reorder.h): the device matrix is P A P'. Same boundary as cell space
+  // with n == n_api: node2cell = perm (node -> device row), cell2node = 1 + the node of a device row.
+  bool reordered = false;
+  double reorder_ms = 0.0, span_before = 0.0, span_after = 0.0;
+  DBuf entry_map;                     // reordered: [nnz] entry of the device matrix for every upper-triangular entry of the
+                                      // caller's, -1 elsewhere (branch currents; built on first use)
+  bool translated() const { return cellspace || reordered; }
   // Rasters set up through the lattice pipeline (lattice_setup.h) hold NO CSR form of the fine-level matrix: resistance-
   // only pair solves never touch one. Entry points that do (current maps, explicit residual checks of full solutions,
   // region pairs, components, the product hooks) build it from the lattice form on first use (ensure_csr).
@@ -386,7 +397,7 @@ struct Solver : ISolver {
   }
   const Dia<T>* dia_ptr() const { return dia.n > 0 ? &dia : nullptr; }
 
-  // ---- boundary translation (no-ops unless cellspace) ----------------------------------------------------------------
+  // ---- boundary translation (no-ops unless cellspace or reordered) ----------------------------------------------------------------
   // node ids of the caller -> row ids of the device matrix
   struct Ids {
     const int64_t* p = nullptr;
@@ -396,7 +407,7 @@ struct Solver : ISolver {
   Ids rows_of(const int64_t* ids, int64_t cnt) {
     Ids r;
     r.p = ids;
-    if (!cellspace || cnt <= 0) return r;
+    if (!translated() || cnt <= 0) return r;
     DBuf in = dalloc<int64_t>((size_t)cnt), out = dalloc<int64_t>((size_t)cnt);
     CS_HIP(hipMemcpyAsync(in.p, ids, (size_t)cnt * sizeof(int64_t), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(map_ids_kernel, dim3(grid_for(cnt)), dim3(256), 0, st, cnt, (const int64_t*)dptr<int64_t>(in),
@@ -409,7 +420,7 @@ struct Solver : ISolver {
   }
   // host column-major n_api x ncols  ->  device column-major n x ncols (zeros at the NODATA rows)
   void upload_cols(const T* host, int64_t ncols, T* dev) {
-    if (!cellspace) {
+    if (!translated()) {
       CS_HIP(hipMemcpyAsync(dev, host, (size_t)n * ncols * sizeof(T), hipMemcpyHostToDevice, st));
       return;
     }
@@ -421,7 +432,7 @@ struct Solver : ISolver {
   }
   // device column-major n x ncols  ->  host column-major n_api x ncols; blocks until the copy has landed
   void download_cols(const T* dev, int64_t ncols, T* host) {
-    if (!cellspace) {
+    if (!translated()) {
       CS_HIP(hipMemcpyAsync(host, dev, (size_t)n * ncols * sizeof(T), hipMemcpyDeviceToHost, st));
       CS_HIP(hipStreamSynchronize(st));
       return;
@@ -432,6 +443,9 @@ struct Solver : ISolver {
     CS_HIP(hipMemcpyAsync(host, tmp.p, tmp.bytes, hipMemcpyDeviceToHost, st));
     CS_HIP(hipStreamSynchronize(st));
   }
+  // reordered handles: something monotone in the caller's id of every device row (1 + that id), which decides the orientation
+  // of a branch in the current kernels (currents.h, upper_entry); null otherwise
+  const int* api_order() const { return reordered ? (const int*)dptr<int>(cell2node) : (const int*)nullptr; }
   const int* raster_rowmap() const { return cellspace ? (const int*)dptr<int>(cellmap) : (const int*)dptr<int>(nodemap); }
 
   // Lattice form of the CG matrix: period known (raster built here, every cell valid) or detected from the band
@@ -696,9 +710,67 @@ struct Solver : ISolver {
       if (hi > 0.0 && lo < 1e300) contrast = hi / lo;
     }
     if (prow && pcol && setup_cellspace_from_csr(A, prow, pcol)) return;
-    finish_setup(std::move(A), prow, pcol, 0);
+    int known_period = 0, expander_verdict = 0;
+    if (kn.reorder && !prow && nnz > 0) reorder_at_setup(A, known_period, expander_verdict);
+    finish_setup(std::move(A), prow, pcol, known_period, nullptr, expander_verdict);
     // (rasters -- lattice detected, strength test run -- are judged by that test: hetero_frac >= 0)
     if (contrast > 1e5 && H.hetero_frac < 0.0) H.hetero_frac = 1.0;
+  }
+
+  // csgpu_opts.reorder on a general CSR handle: ordering and B = P A P' on the device (reorder.h), before the hierarchy is
+  // built, so that the whole set-up runs on the ordered matrix. Not applied -- A untouched, reordered stays false -- to a
+  // matrix with the lattice structure of an all-valid raster (it has locality; known_period then saves finish_setup the
+  // second detection), to a graph that comes with raster coordinates (the caller of this function checks) and to an expander
+  // (the expansion probe, which amg_setup would run on the same graph: its verdict is handed on, so it runs once).
+  void reorder_at_setup(Csr<T>& A, int& known_period, int& expander_verdict) {
+    hipEvent_t e0, e1;
+    CS_HIP(hipEventCreate(&e0));
+    CS_HIP(hipEventCreate(&e1));
+    CS_HIP(hipEventRecord(e0, st));
+    auto stop = [&]() {
+      CS_HIP(hipEventRecord(e1, st));
+      CS_HIP(hipEventSynchronize(e1));
+      float ms = 0;
+      CS_HIP(hipEventElapsedTime(&ms, e0, e1));
+      reorder_ms = ms;
+      hipEventDestroy(e0);
+      hipEventDestroy(e1);
+    };
+    detect_lattice(A, 0);
+    if (dia.n > 0) {
+      known_period = dia.R;
+      if (kn.verbose) fprintf(stderr, "csgpu: reorder: lattice matrix, left as it is\n");
+      return stop();
+    }
+    known_period = -1;  // (no lattice: not looked for again, neither here nor in the reordered matrix)
+    // the conditions under which amg_setup_levels probes (no coordinates here)
+    if (kn.expander_probe && opts.theta == 0.0 && n >= 100000 && n > opts.max_coarse && opts.max_levels > 1) {
+      expander_verdict = expander_probe_says_expander(A, st) ? 1 : -1;
+      if (expander_verdict > 0) {
+        if (kn.verbose) fprintf(stderr, "csgpu: reorder: expander, no locality to restore\n");
+        return stop();
+      }
+    }
+    span_before = mean_span(A, st);
+    ReorderResult ro;
+    reorder_compute<T>((int)n, A.rp(), A.ci(), A.va(), ro, st);
+    Csr<T> B;
+    permute_symmetric(A, (const int*)dptr<int>(ro.perm), (const int*)dptr<int>(ro.order), B, st);
+    A = std::move(B);
+    span_after = mean_span(A, st);
+    node2cell = std::move(ro.perm);
+    cell2node = dalloc<int>((size_t)n);
+    hipLaunchKernelGGL(reorder_plus_one_kernel, dim3(grid_for(n)), dim3(256), 0, st, (int)n, (const int*)dptr<int>(ro.order),
+                       dptr<int>(cell2node));
+    comp_label_api = std::move(ro.comp);  // (found on the caller's numbering: csgpu_components' answer as it stands)
+    ncomp_api = ro.ncomp;
+    check_launch("reorder");
+    CS_HIP(hipStreamSynchronize(st));  // ro.order is released on return
+    reordered = true;
+    stop();
+    if (kn.verbose)
+      fprintf(stderr, "csgpu: reorder: %lld nodes, %d components, %d BFS launches, mean |col - row| / n %.3g -> %.3g, %.2f ms\n",
+              (long long)n, ro.ncomp, ro.levels, span_before, span_after, reorder_ms);
   }
 
   // The Julia host path for rasters WITH NODATA cells (lattice_setup.h, csr_to_cell_dia_kernel): a compact CSR Laplacian
@@ -779,7 +851,8 @@ struct Solver : ISolver {
   }
 
   // known_period: raster height when the matrix was built here from an all-valid raster, 0 = detect, -1 = no lattice
-  void finish_setup(Csr<T>&& A, const int* prow, const int* pcol, int known_period, const long long* size0 = nullptr) {
+  void finish_setup(Csr<T>&& A, const int* prow, const int* pcol, int known_period, const long long* size0 = nullptr,
+                    int expander_verdict = 0) {
     detect_lattice(A, known_period);
     DBuf lrow, lcol;
     // A lattice detected from the matrix numbers ITS nodes column-major on an R x (n / R) raster; coordinates the caller
@@ -798,6 +871,7 @@ struct Solver : ISolver {
     SetupParams sp = setup_params();
     sp.size0 = size0;
     sp.n_real = size0 ? n_api : 0;
+    sp.expander_verdict = expander_verdict;
     if (dia.n > 0) {  // raster extent known: left-over cells stay with their own 3x3 tile (agg_pass2_kernel)
       sp.grid_rows = dia.R;
       sp.grid_cols = (int)(n / dia.R);
@@ -1485,6 +1559,15 @@ struct Solver : ISolver {
 
   void ensure_components() {
     if (ncomp >= 0) return;
+    if (reordered) {  // found at set-up on the caller's numbering: the label of a device row is that of its node
+      comp_label.alloc((size_t)n * sizeof(int));
+      hipLaunchKernelGGL(reorder_scatter_int_kernel, dim3(grid_for(n)), dim3(256), 0, st, (int)n, (const int*)dptr<int>(node2cell),
+                         (const int*)dptr<int>(comp_label_api), dptr<int>(comp_label));
+      check_launch("components (reordered)");
+      CS_HIP(hipStreamSynchronize(st));
+      ncomp = ncomp_api;
+      return;
+    }
     ensure_csr();
     const Csr<T>& A = cg_matrix();
     comp_label.alloc((size_t)n * sizeof(int));
@@ -1497,6 +1580,10 @@ struct Solver : ISolver {
     KnobScope ks(&kn);
     CS_HIP(hipSetDevice(device));
     ensure_components();
+    if (reordered) {
+      if (out) CS_HIP(hipMemcpy(out, comp_label_api.p, (size_t)n_api * sizeof(int), hipMemcpyDeviceToHost));
+      return ncomp_api;
+    }
     if (!cellspace) {
       if (out) CS_HIP(hipMemcpy(out, comp_label.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
       return ncomp;
@@ -1518,6 +1605,17 @@ struct Solver : ISolver {
     }
     if (out) CS_HIP(hipMemcpy(out, comp_label_api.p, (size_t)n_api * sizeof(int), hipMemcpyDeviceToHost));
     return ncomp_api;
+  }
+
+  // perm_out[node] = device row (identity unless the handle was reordered)
+  void get_permutation(int32_t* out) override {
+    std::lock_guard<std::mutex> lk(mu);
+    if (reordered) {
+      CS_HIP(hipSetDevice(device));
+      CS_HIP(hipMemcpy(out, node2cell.p, (size_t)n_api * sizeof(int), hipMemcpyDeviceToHost));
+      return;
+    }
+    for (int64_t i = 0; i < n_api; ++i) out[i] = (int32_t)i;
   }
 
   // Advanced-mode solve on a raster-built handle, rasters in and out (compute_omniscape_current, utils.jl:145-257, for
@@ -1584,7 +1682,8 @@ struct Solver : ISolver {
                          (const T*)dptr<T>(W.x), (const int*)dptr<int>(comp_label), dptr<unsigned long long>(cmax));
       hipLaunchKernelGGL((node_current_kernel<T, 1>), dim3(gc), dim3(256), 0, st, (int)n, A.rp(), A.ci(), A.va(),
                          (const T*)dptr<T>(W.x), (const double*)nullptr, dptr<T>(dcurr), gnode,
-                         (const int*)dptr<int>(comp_label), (const unsigned long long*)dptr<unsigned long long>(cmax));
+                         (const int*)dptr<int>(comp_label), (const unsigned long long*)dptr<unsigned long long>(cmax),
+                         (const int*)nullptr);
       hipLaunchKernelGGL((raster_scatter_kernel<T>), dim3(grid_for(ncells)), dim3(256), 0, st, ncells,
                          raster_rowmap(), (const T*)dptr<T>(dcurr), dptr<T>(draster));
       CS_HIP(hipMemcpyAsync(curr_out, draster.p, (size_t)ncells * sizeof(T), hipMemcpyDeviceToHost, st));
@@ -1796,6 +1895,8 @@ struct Solver : ISolver {
     if (!need_x) focal.resize((size_t)ngather + 2 * Kmax);
     DBuf dcurr, dcum, dmax, dweight, dbpart, dbmax, dbranch, dbranch2;
     if (branch_out) {
+      if (reordered && !entry_map.p)
+        build_entry_map(cg_matrix(), (const int*)dptr<int>(node2cell), (const int*)dptr<int>(cell2node), entry_map, st);
       dbranch.alloc((size_t)std::max<int64_t>(nnz, 1) * Kmax * sizeof(T));
       dbranch2.alloc((size_t)std::max<int64_t>(nnz, 1) * Kmax * sizeof(T));
     }
@@ -1891,20 +1992,26 @@ struct Solver : ISolver {
         const Csr<T>& A = cg_matrix();
         const int gc = grid_for(n * K);
         CS_DISPATCH_K(K, hipLaunchKernelGGL((branch_max_kernel<T, KK>), dim3(gc), dim3(256), 0, st, (int)n, A.rp(), A.ci(),
-                                            A.va(), (const T*)dptr<T>(W.x), dptr<double>(dbpart)));
+                                            A.va(), (const T*)dptr<T>(W.x), dptr<double>(dbpart), api_order()));
         CS_DISPATCH_K(K, hipLaunchKernelGGL((branch_max_final_kernel<KK>), dim3(1), dim3(256), 0, st,
                                             (const double*)dptr<double>(dbpart), gc, dptr<double>(dbmax)));
         CS_DISPATCH_K(K, hipLaunchKernelGGL((node_current_kernel<T, KK>), dim3(gc), dim3(256), 0, st, (int)n, A.rp(), A.ci(),
                                             A.va(), (const T*)dptr<T>(W.x), (const double*)dptr<double>(dbmax),
                                             dptr<T>(dcurr), (const T*)nullptr, (const int*)nullptr,
-                                            (const unsigned long long*)nullptr));
+                                            (const unsigned long long*)nullptr, api_order()));
         if (branch_out) {
           CS_DISPATCH_K(K, hipLaunchKernelGGL((branch_current_kernel<T, KK>), dim3(gc), dim3(256), 0, st, (int)n, A.rp(), A.ci(),
                                               A.va(), (const T*)dptr<T>(W.x), (const double*)dptr<double>(dbmax),
-                                              dptr<T>(dbranch)));
+                                              dptr<T>(dbranch), api_order()));
           CS_DISPATCH_K(K, hipLaunchKernelGGL((deinterleave_kernel<T, KK>), dim3(grid_for(nnz * ncols)), dim3(256), 0, st, nnz,
                                               (const T*)dptr<T>(dbranch), ncols, dptr<T>(dbranch2)));
-          CS_HIP(hipMemcpyAsync((T*)branch_out + (size_t)p0 * nnz, dbranch2.p, (size_t)nnz * ncols * sizeof(T),
+          const T* bsrc = dptr<T>(dbranch2);
+          if (reordered) {  // back to the caller's entry positions ([ncols][nnz] both; dbranch is free again)
+            hipLaunchKernelGGL((gather_entries_kernel<T>), dim3(grid_for(nnz * ncols)), dim3(256), 0, st, nnz, ncols,
+                               (const int*)dptr<int>(entry_map), (const T*)dptr<T>(dbranch2), dptr<T>(dbranch));
+            bsrc = dptr<T>(dbranch);
+          }
+          CS_HIP(hipMemcpyAsync((T*)branch_out + (size_t)p0 * nnz, bsrc, (size_t)nnz * ncols * sizeof(T),
                                 hipMemcpyDeviceToHost, st));
         }
         if (curr_out) {
@@ -2143,13 +2250,13 @@ struct Solver : ISolver {
         const Csr<T>& A = cg_matrix();
         const int gc = grid_for(n * K);
         CS_DISPATCH_K(K, hipLaunchKernelGGL((branch_max_kernel<T, KK>), dim3(gc), dim3(256), 0, st, (int)n, A.rp(), A.ci(),
-                                            A.va(), (const T*)dptr<T>(W.x), dptr<double>(dbpart)));
+                                            A.va(), (const T*)dptr<T>(W.x), dptr<double>(dbpart), api_order()));
         CS_DISPATCH_K(K, hipLaunchKernelGGL((branch_max_final_kernel<KK>), dim3(1), dim3(256), 0, st,
                                             (const double*)dptr<double>(dbpart), gc, dptr<double>(dbmax)));
         CS_DISPATCH_K(K, hipLaunchKernelGGL((node_current_kernel<T, KK>), dim3(gc), dim3(256), 0, st, (int)n, A.rp(), A.ci(),
                                             A.va(), (const T*)dptr<T>(W.x), (const double*)dptr<double>(dbmax),
                                             dptr<T>(dcurr), (const T*)nullptr, (const int*)nullptr,
-                                            (const unsigned long long*)nullptr));
+                                            (const unsigned long long*)nullptr, api_order()));
         if (J.curr_out) {
           CS_HIP(hipStreamSynchronize(st));  // stage still feeds the copy of x
           CS_DISPATCH_K(K, hipLaunchKernelGGL((deinterleave_kernel<T, KK>), dim3(grid_for(n * ncols)), dim3(256), 0, st, n,
@@ -2374,6 +2481,10 @@ struct Solver : ISolver {
     info->fused_restrict_solves = H.fused_restrict_solves;
     info->virtual_rhs_solves = H.virtual_rhs_solves;
     info->reserved_info3 = 0;
+    info->reordered = reordered ? 1 : 0;
+    info->reorder_ms = reorder_ms;
+    info->span_before = span_before;
+    info->span_after = span_after;
     info->enrich_tau = kn.enrich ? kn.enrich_tau : 0.0;
     for (size_t l = 0; l < H.levels.size(); ++l) {
       const Level<TP>& L = H.levels[l];
@@ -2400,7 +2511,7 @@ struct Solver : ISolver {
     bytes += (int64_t)(H.coarse_inv.bytes + W.x.bytes + W.r.bytes + W.z.bytes + W.rp.bytes + W.p.bytes + W.Ap.bytes + W.b.bytes);
     info->operator_complexity = nnz_sum / std::max(1.0, (double)nnz);
     info->grid_complexity = n_sum / std::max(1.0, (double)H.levels[0].A.nrows);
-    info->setup_ms = H.setup_ms;
+    info->setup_ms = H.setup_ms + reorder_ms;  // (the ordering is part of the set-up's cost)
     info->upload_ms = upload_ms;
     info->device_bytes = bytes;
     const int64_t csr_bytes_k1 = nnz * (int64_t)(sizeof(T) + 4) + (n + 1) * 4 + 2 * n * (int64_t)sizeof(T);
@@ -2466,7 +2577,7 @@ struct Solver : ISolver {
     ensure_csr();
     const Csr<T>& A = cg_matrix();
     DBuf x((size_t)n * k * sizeof(T)), y((size_t)n * k * sizeof(T));
-    if (cellspace) {
+    if (translated()) {
       // host vectors are interleaved [n_api][k] in the caller's numbering: (node, column) pairs are "columns" of length k
       // for the translation kernels when the roles of the two indices are swapped -- simplest: go through column-major
       DBuf xc((size_t)n * k * sizeof(T)), t((size_t)n_api * k * sizeof(T)), t2((size_t)n_api * k * sizeof(T));
@@ -2787,7 +2898,7 @@ void csgpu_default_opts(csgpu_opts* o) {
   o->two_product = 0;
   o->stencil = 0;
   o->explicit_check = 0;
-  o->reserved3 = 0;
+  o->reorder = 0;
 }
 
 // host_matrix: csgpu_setup / csgpu_multi_setup -- 2^31 stored entries and more are streamed (setup_from_host_streamed),
@@ -3030,6 +3141,17 @@ int csgpu_components(csgpu_handle* h, int32_t* component_out, int64_t* ncomponen
   }
   const int64_t nc = h->solver->components(component_out);
   if (ncomponents) *ncomponents = nc;
+  return CSGPU_OK;
+  CS_API_END
+}
+
+int csgpu_get_permutation(const csgpu_handle* h, int32_t* perm_out) {
+  CS_API_BEGIN
+  if (!h || !perm_out) {
+    g_last_error = "null handle or output";
+    return CSGPU_BAD_ARGS;
+  }
+  h->solver->get_permutation(perm_out);
   return CSGPU_OK;
   CS_API_END
 }

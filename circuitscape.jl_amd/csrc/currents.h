@@ -14,11 +14,19 @@
 
 namespace csgpu {
 
+// Orientation of a stored entry. The reference orients every branch by the CALLER's node ids (upper triangle: row < col). On a
+// handle whose device rows are a permutation of the caller's nodes (reorder.h) `ord[device row]` is monotone in the caller's id
+// of that row and decides; null = the device numbering is the caller's.
+__device__ __forceinline__ bool upper_entry(int row, int col, const int* __restrict__ ord) {
+  return ord ? ord[col] > ord[row] : col > row;
+}
+
 // pass 1: per-block partial maxima of the signed branch currents in both orientations -> part[block][K][2]
 template <class T, int K>
 __global__ __launch_bounds__(256) void branch_max_kernel(int n, const int* __restrict__ rp, const int* __restrict__ ci,
                                                          const T* __restrict__ va, const T* __restrict__ x,
-                                                         double* __restrict__ part) {
+                                                         double* __restrict__ part,
+                                                         const int* __restrict__ ord) {
   __shared__ double sm[2][4][K];
   const int c = threadIdx.x % K;
   double mpos = -1e300, mneg = -1e300;
@@ -28,7 +36,7 @@ __global__ __launch_bounds__(256) void branch_max_kernel(int n, const int* __res
     const double vr = (double)x[(size_t)row * K + c];
     for (int k = rp[row]; k < rp[row + 1]; ++k) {
       const int col = ci[k];
-      if (col > row) {  // each undirected edge once, oriented (row < col) like the reference's upper triangle
+      if (upper_entry(row, col, ord)) {  // each undirected edge once, oriented (row < col) like the reference's upper triangle
         const double g = fabs((double)va[k]);
         const double b = g * (vr - (double)x[(size_t)col * K + c]);
         mpos = b > mpos ? b : mpos;
@@ -130,7 +138,8 @@ __global__ __launch_bounds__(256) void node_current_kernel(int n, const int* __r
                                                            const double* __restrict__ maxcur, T* __restrict__ curr,
                                                            const T* __restrict__ ground,
                                                            const int* __restrict__ comp,
-                                                           const unsigned long long* __restrict__ compmax) {
+                                                           const unsigned long long* __restrict__ compmax,
+                                                           const int* __restrict__ ord) {
   const int c = threadIdx.x % K;
   double mp = maxcur ? maxcur[2 * c] : 0.0, mn = maxcur ? maxcur[2 * c + 1] : 0.0;
   const int64_t total = (int64_t)n * K;
@@ -147,12 +156,13 @@ __global__ __launch_bounds__(256) void node_current_kernel(int n, const int* __r
       if (col == row) continue;
       const double g = fabs((double)va[k]);
       // signed branch current of the edge in the reference's upper-triangular orientation (smaller index first)
-      const double bpos = col > row ? g * (vr - (double)x[(size_t)col * K + c]) : g * ((double)x[(size_t)col * K + c] - vr);
+      const bool up = upper_entry(row, col, ord);
+      const double bpos = up ? g * (vr - (double)x[(size_t)col * K + c]) : g * ((double)x[(size_t)col * K + c] - vr);
       const double keep_pos = !(fabs(bpos / mp) < 1e-8) ? bpos : 0.0;     // entry of B  (pos orientation)
       const double keep_neg = !(fabs(-bpos / mn) < 1e-8) ? -bpos : 0.0;   // entry of B' (neg orientation)
       // flow from `col` into `row`:  pos orientation contributes g (v_col - v_row), neg orientation g (v_row - v_col)
-      const double into = col > row ? -keep_pos : keep_pos;   // g (v_col - v_row), thresholded with maxcur_pos
-      const double outof = col > row ? -keep_neg : keep_neg;  // g (v_row - v_col), thresholded with maxcur_neg
+      const double into = up ? -keep_pos : keep_pos;   // g (v_col - v_row), thresholded with maxcur_pos
+      const double outof = up ? -keep_neg : keep_neg;  // g (v_row - v_col), thresholded with maxcur_neg
       if (into > 0.0) in += into;
       if (outof > 0.0) out += outof;
     }
@@ -172,7 +182,8 @@ __global__ __launch_bounds__(256) void node_current_kernel(int n, const int* __r
 template <class T, int K>
 __global__ __launch_bounds__(256) void branch_current_kernel(int n, const int* __restrict__ rp, const int* __restrict__ ci,
                                                              const T* __restrict__ va, const T* __restrict__ x,
-                                                             const double* __restrict__ maxcur, T* __restrict__ out) {
+                                                             const double* __restrict__ maxcur, T* __restrict__ out,
+                                                             const int* __restrict__ ord) {
   const int c = threadIdx.x % K;
   const double mp = maxcur[2 * c];
   const int64_t total = (int64_t)n * K;
@@ -182,7 +193,7 @@ __global__ __launch_bounds__(256) void branch_current_kernel(int n, const int* _
     for (int k = rp[row]; k < rp[row + 1]; ++k) {
       const int col = ci[k];
       double b = 0.0;
-      if (col > row) {
+      if (upper_entry(row, col, ord)) {
         b = fabs((double)va[k]) * (vr - (double)x[(size_t)col * K + c]);
         if (fabs(b / mp) < 1e-8) b = 0.0;
       }

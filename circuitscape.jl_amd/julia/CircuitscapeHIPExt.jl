@@ -20,7 +20,7 @@ mutable struct CsgpuOpts
     theta::Float64; omega_p::Float64; omega_s::Float64; rtol::Float64; atol::Float64
     node_row::Ptr{Int32}; node_col::Ptr{Int32}
     precond_bytes::Int32; use_graph::Int32; two_product::Int32; stencil::Int32
-    explicit_check::Int32; reserved3::Int32
+    explicit_check::Int32; reorder::Int32
     # round 6: the decisions that used to be environment switches (include/csgpu.h, 0 = the default in every field)
     last_level_sweeps::Int32; enrich::Int32; enrich_steps::Int32; dia25_min_rows::Int32; dia25_prefetch::Int32
     dia25_waves::Int32; dia25_fused_j0::Int32; stream::Int32; tail_rows::Int32; poly_lattice::Int32; cellspace::Int32

@@ -22,7 +22,7 @@ AGG_AUTO, AGG_MIS2, AGG_GRID = 0, 1, 2
 EXPORTS = [
     "csgpu_device_count", "csgpu_default_opts", "csgpu_setup", "csgpu_raster_setup", "csgpu_get_info",
     "csgpu_solve_pairs", "csgpu_solve_pairs_currents", "csgpu_solve_rhs", "csgpu_solve_grounded", "csgpu_solve_sources", "csgpu_solve_region_pairs", "csgpu_spmv_bench", "csgpu_spmv_host", "csgpu_level_spmv_host",
-    "csgpu_get_level_matrix", "csgpu_raster_nodemap", "csgpu_components", "csgpu_raster_setup_grounded", "csgpu_raster_setup_poly",
+    "csgpu_get_level_matrix", "csgpu_get_permutation", "csgpu_raster_nodemap", "csgpu_components", "csgpu_raster_setup_grounded", "csgpu_raster_setup_poly",
     "csgpu_solve_raster", "csgpu_dia_product_host",
     "csgpu_multi_setup", "csgpu_multi_raster_setup", "csgpu_multi_solve_pairs", "csgpu_multi_solve_pairs_currents",
     "csgpu_multi_solve_grounded", "csgpu_multi_solve_sources", "csgpu_multi_device_count",
@@ -59,7 +59,7 @@ class Opts(ctypes.Structure):
         ("node_row", ctypes.c_void_p), ("node_col", ctypes.c_void_p),
         ("precond_bytes", ctypes.c_int32), ("use_graph", ctypes.c_int32),
         ("two_product", ctypes.c_int32), ("stencil", ctypes.c_int32),
-        ("explicit_check", ctypes.c_int32), ("reserved3", ctypes.c_int32),
+        ("explicit_check", ctypes.c_int32), ("reorder", ctypes.c_int32),
     ] + [(name, ctypes.c_int32) for name in OPTS_INT_FIELDS] + [
         ("stream_min", ctypes.c_int64), ("host_stream_block", ctypes.c_int64),
     ] + [(name, ctypes.c_double) for name in OPTS_DOUBLE_FIELDS]
@@ -74,11 +74,12 @@ class Info(ctypes.Structure):
         ("level_n", ctypes.c_int64 * 32), ("level_nnz", ctypes.c_int64 * 32),
         ("spmv_bytes_fine", ctypes.c_int64), ("bytes_per_iteration", ctypes.c_int64),
         ("level_form", ctypes.c_int32 * 32), ("hierarchy_rebuilt_fp64", ctypes.c_int32),
-        ("enrich_vectors", ctypes.c_int32), ("host_blocks", ctypes.c_int32), ("reserved_info", ctypes.c_int32),
+        ("enrich_vectors", ctypes.c_int32), ("host_blocks", ctypes.c_int32), ("reordered", ctypes.c_int32),
         ("batch_width", ctypes.c_int32), ("stream_mode", ctypes.c_int32), ("tail_first_level", ctypes.c_int32),
         ("last_level_sweeps", ctypes.c_int32), ("coarse_chebyshev", ctypes.c_int32), ("cellspace", ctypes.c_int32),
         ("poly_lattice", ctypes.c_int32), ("enrich_on", ctypes.c_int32), ("enrich_tau", ctypes.c_double),
         ("expander_probe_hit", ctypes.c_int32), ("fused_restrict_solves", ctypes.c_int32), ("virtual_rhs_solves", ctypes.c_int32), ("reserved_info3", ctypes.c_int32),
+        ("reorder_ms", ctypes.c_double), ("span_before", ctypes.c_double), ("span_after", ctypes.c_double),
     ]
 
 
@@ -129,6 +130,7 @@ def _bind(L):
     L.csgpu_solve_raster.argtypes = [vp, vp, vp, vp, ctypes.POINTER(Stats)]
     L.csgpu_get_level_matrix.argtypes = [vp, i32, i32, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64),
                                          vp, vp, vp]
+    L.csgpu_get_permutation.argtypes = [vp, vp]
     L.csgpu_dia_product_host.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp]
     L.csgpu_multi_setup.argtypes = [vp, vp, vp, i64, i64, i32, i32, i32, ctypes.POINTER(Opts), vp, i32, ctypes.POINTER(vp)]
     L.csgpu_multi_raster_setup.argtypes = [vp, i64, i64, i32, i32, i32, i32, ctypes.POINTER(Opts), vp, i32, ctypes.POINTER(vp)]
@@ -427,6 +429,13 @@ class Handle:
         _check(lib().csgpu_components(self._p, lab.ctypes.data, ctypes.byref(nc)))
         return lab, nc.value
 
+    def permutation(self):
+        """csgpu_get_permutation: perm[node] = device row (int32, length n); the identity unless the handle was set up with
+        `reorder=1` and info["reordered"] == 1. Node ids and vectors of every other method stay in the caller's numbering."""
+        perm = np.zeros(self.info["n"], dtype=np.int32)
+        _check(lib().csgpu_get_permutation(self._p, perm.ctypes.data))
+        return perm
+
     def level_spmv(self, lvl, which, x):
         """y = (level operator) x through the V-cycle's launcher for that operator; returns (y, dots) where dots is
         the fused x[:n].y per column for which == "M", else None. x has shape (ncols,) or (ncols, k)."""
@@ -520,6 +529,12 @@ class MultiHandle:
         i = Info()
         _check(lib().csgpu_get_info(lib().csgpu_multi_handle(self._p, slot), ctypes.byref(i)))
         return {k: getattr(i, k) for k, _ in Info._fields_ if k not in ("level_n", "level_nnz", "level_form")}
+
+    def permutation(self, slot=0):
+        """Handle.permutation() of the replica in device slot `slot` (replicas reorder alike)."""
+        perm = np.zeros(self.info(slot)["n"], dtype=np.int32)
+        _check(lib().csgpu_get_permutation(lib().csgpu_multi_handle(self._p, slot), perm.ctypes.data))
+        return perm
 
     def solve_pairs(self, src, dst, gather=None):
         """As Handle.solve_pairs (no voltages). Returns (resistances, gathered or None, stats dict incl. the per-device

@@ -33,9 +33,12 @@ HIP = ["hip", "hip+amg", "cg+amg+hip", "mi355x"]
 
 @dataclass
 class HIPAMGSolver:
-    """AMG-preconditioned CG on the MI355X; `bs` = right-hand sides per SpMM batch (cf. CholmodSolver.bs)."""
+    """AMG-preconditioned CG on the MI355X; `bs` = right-hand sides per SpMM batch (cf. CholmodSolver.bs).
+    `opts` are csgpu_opts overrides handed to lib.default_opts, e.g. HIPAMGSolver(opts={"reorder": 1}): network graphs are
+    renumbered for locality on the device at set-up (include/csgpu.h, csgpu_opts.reorder; node ids, tables and maps keep the
+    caller's numbering; off by default)."""
     bs: int = 8
-    opts: dict = field(default_factory=dict)  # extra csgpu_opts overrides (rtol, criterion, theta, ...)
+    opts: dict = field(default_factory=dict)  # extra csgpu_opts overrides (rtol, criterion, theta, reorder, ...)
 
 
 @dataclass

@@ -48,7 +48,7 @@
  *                              the raster branch of advanced_kernel (src/raster/advanced.jl:151-271) for rasters
  *                              without polygons: grounded matrix, right-hand side from the source raster, node
  *                              currents incl. ground currents (src/out.jl:178-207), maps back -- "next" rows N2/N3
- *   csgpu_get_info, csgpu_spmv_bench, csgpu_spmv_host, csgpu_level_spmv_host, csgpu_get_level_matrix,
+ *   csgpu_get_info, csgpu_get_permutation, csgpu_spmv_bench, csgpu_spmv_host, csgpu_level_spmv_host, csgpu_get_level_matrix,
  *   csgpu_dia_product_host <-> no reference counterpart: measurement and test hooks
  *
  * Conventions
@@ -166,13 +166,23 @@ typedef struct csgpu_opts {
    * solution vector and evaluate ||A x - b|| / ||b|| with an explicit product, as every other entry point does.
    * Default 0. */
   int32_t explicit_check;
-  int32_t reserved3;
+  /* Locality reordering of network graphs (csrc/reorder.h): 1 = a handle set up from a general CSR matrix (csgpu_setup,
+   * csgpu_multi_setup) numbers its device rows by breadth-first level sets (Cuthill-McKee style: one search per connected
+   * component from a pseudo-peripheral node, levels refined by first neighbour), computed and applied on the device at
+   * set-up; the hierarchy is built from P A P'. EVERY entry point keeps speaking the caller's numbering -- node ids, n-vectors,
+   * branch_out positions, component labels -- so results are those of the unordered handle to the solve tolerance; only
+   * csgpu_get_level_matrix / csgpu_level_spmv_host show the device numbering. Not applied (csgpu_info.reordered = 0) to
+   * matrices with the lattice structure of a raster, to matrices that come with node_row / node_col, to streamed host
+   * matrices, to raster handles, and to graphs the expansion probe calls expanders (no locality to restore).
+   * 0 = off (default). CSGPU_REORDER=0/1 is the debug override. */
+  int32_t reorder;
   /* ---- Round 6: every decision that used to be an environment switch inside the library. 0 = the
    * library's default in every field; csgpu_default_opts writes zeros. The CSGPU_* environment variables that carried these
    * choices remain as DEBUG overrides only: they are read ONCE, when a handle is set up (csrc/csgpu.hip: knobs_from_opts),
    * never on a call path, and a handle keeps what it was set up with -- two handles of one process may differ.
    * csgpu_get_info reports what a handle ended up with (level_form, enrich_vectors, hierarchy_rebuilt_fp64, host_blocks,
-   * batch_width, stream_mode, tail_first_level, last_level_sweeps, coarse_chebyshev, cellspace, poly_lattice, expander_probe_hit). */
+   * batch_width, stream_mode, tail_first_level, last_level_sweeps, coarse_chebyshev, cellspace, poly_lattice, expander_probe_hit,
+   * reordered). */
   int32_t last_level_sweeps;  /* damped-Jacobi sweeps that stand in for the coarsest solve when the last level is too large
                                  for a dense inverse. A hierarchy of ONE level -- a graph the set-up declines to coarsen,
                                  BASELINE configs[4] -- is then CG with a polynomial preconditioner of that degree: every sweep
@@ -285,7 +295,7 @@ typedef struct csgpu_info {
   int32_t host_blocks;          /* > 0: the host matrix of csgpu_setup was streamed to the device in this many blocks of rows and
                                    scattered straight into the lattice form (matrices with 2^31 stored entries and more; the
                                    device holds no CSR form of it); 0 = any other set-up */
-  int32_t reserved_info;
+  int32_t reordered;            /* 1 = the device rows are a permutation of the caller's nodes (csgpu_opts.reorder; csgpu_get_permutation) */
   /* round 6: the choices a handle ended up with (options, defaults and debug overrides resolved at set-up) */
   int32_t batch_width;          /* columns of a full batch (opts.batch after the K <= 16 rule of fp64 CSR-path handles) */
   int32_t stream_mode;          /* csgpu_opts.stream as resolved: 0 auto, 1 always, -1 never */
@@ -300,6 +310,10 @@ typedef struct csgpu_info {
   int32_t fused_restrict_solves; /* batches so far whose PCG ran the fused residual update + restriction (csgpu_opts.fused_restrict) */
   int32_t virtual_rhs_solves;    /* ... of which the right-hand side was never stored (csgpu_opts.sparse_init) */
   int32_t reserved_info3;
+  double reorder_ms;            /* csgpu_opts.reorder: HIP-event time of the ordering and of the permutation of the matrix (incl. the
+                                   lattice / expansion checks that decide whether to reorder); INCLUDED in setup_ms */
+  double span_before;           /* reordered handles: mean |col - row| / n over the stored entries of the matrix as given ... */
+  double span_after;            /* ... and of the device matrix P A P' (0 when not reordered) */
 } csgpu_info;
 
 typedef struct csgpu_stats {
@@ -408,6 +422,10 @@ int csgpu_components(csgpu_handle* h, int32_t* component_out, int64_t* ncomponen
 
 int csgpu_get_info(const csgpu_handle* h, csgpu_info* info);
 
+/* Test / diagnostic hook of csgpu_opts.reorder: perm_out[node] = device row of the caller's node (csgpu_get_info().n entries);
+ * the identity when csgpu_get_info().reordered == 0. */
+int csgpu_get_permutation(const csgpu_handle* h, int32_t* perm_out);
+
 /* Solve A v = e_dst - e_src for every pair (0-based node ids), batched `opts.batch` at a time.
  *   resist_out[p]              = v[dst_p] - v[src_p]                                  (core.jl:232), may be NULL
  *   gathered_out[p*ngather+g]  = v[gather_idx[g]] - v[src_p]                         (may be NULL / ngather 0)
@@ -510,7 +528,8 @@ int csgpu_level_spmv_host(csgpu_handle* h, int lvl, int which, const void* x, vo
 
 /* Copy level `lvl`'s operator (which: 0 = A, 1 = P, 2 = R, 3 = Q, 4 = Q^T, 5 = [S Q]; the
  * last two exist on level 0 of a two-product hierarchy only) back to the host for inspection by tests.
- * Pass NULL arrays to query sizes only. */
+ * Pass NULL arrays to query sizes only. This hook and csgpu_level_spmv_host look INTO the hierarchy: on a reordered handle
+ * (csgpu_opts.reorder) rows and columns are in the DEVICE numbering, level 0's A is P A P' (csgpu_get_permutation gives P). */
 int csgpu_get_level_matrix(const csgpu_handle* h, int lvl, int which, int64_t* nrows, int64_t* ncols, int64_t* nnz,
                            int32_t* rowptr, int32_t* colidx, void* vals);
 

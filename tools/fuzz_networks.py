@@ -5,7 +5,9 @@ through csgpu_setup (the Julia host path of network problems, network/pairwise.j
 side on a grounded copy (multiple_solve semantics, raster/advanced.jl:282-312), grounded solves on the shared hierarchy and
 node currents, fp64 / fp32 hierarchy, batch 1..5, against direct solves (scipy). The matrix carries the reference's
 regularisation shift eps * norm(nzval) (core.jl:161). Test infrastructure only.
-usage: fuzz_networks.py SEED NCASES    (env CSGPU_LIB: library to load, default the emulator build)"""
+usage: fuzz_networks.py SEED NCASES [--reorder]   (env CSGPU_LIB: library to load, default the emulator build)
+--reorder: every handle is set up with csgpu_opts.reorder = 1 (device-side locality reordering, csrc/reorder.h): the same checks,
+in the caller's numbering, on a permuted device matrix."""
 import os, sys, numpy as np, scipy.sparse as sp, scipy.sparse.linalg as spla
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -13,6 +15,7 @@ import circuitscape_jl_amd  # noqa: E402,F401
 from circuitscape_jl_amd import lib as L  # noqa: E402
 from oracle import refmaps  # noqa: E402
 L.load(os.environ.get("CSGPU_LIB", os.path.join(ROOT, "tests", "emu", "libcsgpu_emu.so")))
+REORDER = 1 if "--reorder" in sys.argv[3:] else 0
 seed0 = int(sys.argv[1]); ncase = int(sys.argv[2])
 NMIN, NMAX = int(os.environ.get("FUZZ_MIN", "5")), int(os.environ.get("FUZZ_MAX", "700"))
 
@@ -96,7 +99,7 @@ for case in range(ncase):
             v = spla.spsolve(A.tocsc(), b) if s != d else np.zeros(nb)
             v = v - v[s]
             Rd[p] = v[d]; Vd.append(v)
-        with L.setup(A, L.default_opts(batch=batch, precond_bytes=pb, rtol=1e-10, atol=0.0)) as h:
+        with L.setup(A, L.default_opts(batch=batch, precond_bytes=pb, rtol=1e-10, atol=0.0, reorder=REORDER)) as h:
             R, _, volt, st = h.solve_pairs(src, dst, want_voltages=True)
             scale = max(np.max(np.abs(Rd)), 1e-300)
             e1 = float(np.max(np.abs(R - Rd)) / scale)
@@ -139,7 +142,7 @@ for case in range(ncase):
         Ag = sp.csr_matrix(A + sp.diags(gd * 10.0 ** rng.uniform(-2, 2)))
         bg = rng.standard_normal(nb)
         xd = spla.spsolve(Ag.tocsc(), bg)
-        with L.setup(Ag, L.default_opts(batch=batch, precond_bytes=pb, rtol=1e-10, atol=0.0)) as h3:
+        with L.setup(Ag, L.default_opts(batch=batch, precond_bytes=pb, rtol=1e-10, atol=0.0, reorder=REORDER)) as h3:
             xg, st3 = h3.solve_rhs(bg)
             e3 = float(np.max(np.abs(xg - xd)) / max(np.max(np.abs(xd)), 1e-300))
             r3 = float(np.linalg.norm(Ag @ xg - bg) / np.linalg.norm(bg))

@@ -2,8 +2,11 @@
 """Does a locality-restoring renumbering of a NETWORK at set-up pay? A random geometric graph (mean
 degree 10) whose node ids carry no locality -- what network mode gets from a file (src/network/pairwise.jl:31-65) --
 solved (a) as given, (b) renumbered on the host by scipy's reverse Cuthill-McKee, (c) renumbered along the true
-coordinates (cells of a sqrt(n)/8 grid, row-major: the best a renumbering could do). Per variant: set-up, 16 pair solves
-from one anchor at batch 16, the CSR SpMM's time / GB/s (algorithmic bytes), iterations. One JSON line per variant."""
+coordinates (cells of a sqrt(n)/8 grid, row-major: the best a renumbering could do), (d) as given with the DEVICE-side
+reordering of the library (csgpu_opts.reorder = 1, csrc/reorder.h: the ordering is then part of the set-up). Per variant:
+set-up, 16 pair solves from one anchor at batch 16, the CSR SpMM's time / GB/s (algorithmic bytes), iterations, and for (d)
+reorder_ms / span_before / span_after from csgpu_get_info. One JSON line per variant.
+    network_renumber_ab.py [n] [repetitions]     the whole sequence `repetitions` times in one process (default 1)"""
 import json
 import os
 import sys
@@ -23,6 +26,7 @@ def main():
     from scipy.spatial import cKDTree
     import torch
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 1000000
+    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     lib.load(os.environ.get("CSGPU_LIB"))
     dev = torch.device("cuda", 0) if torch.cuda.is_available() else None
     rng = np.random.default_rng(777)
@@ -47,8 +51,10 @@ def main():
     side = max(1, int(np.sqrt(m) / 8))
     cell = (np.minimum((xy[:, 1] * side).astype(np.int64), side - 1) * side + np.minimum((xy[:, 0] * side).astype(np.int64), side - 1))
     variants["sorted by the true coordinates (grid cells, row-major)"] = np.argsort(cell, kind="stable")
+    DEVICE = "device reorder (opts.reorder = 1) on the as-given ids"
+    variants[DEVICE] = np.arange(m)
     ref = None
-    for name, perm in variants.items():
+    for rep_no, (name, perm) in ((r, v) for r in range(reps) for v in variants.items()):
         inv = np.empty(m, dtype=np.int64)
         inv[perm] = np.arange(m)
         A = G[perm][:, perm].tocsr()
@@ -56,7 +62,8 @@ def main():
         src = [int(inv[focal[0]])] * 16
         dst = [int(inv[q]) for q in focal[1:]]
         t0 = time.perf_counter()
-        h = lib.setup(A, lib.default_opts(batch=16, precond_bytes=0), index_dtype=np.int32, index_base=0)
+        h = lib.setup(A, lib.default_opts(batch=16, precond_bytes=0, reorder=1 if name == DEVICE else 0), index_dtype=np.int32,
+                      index_base=0)
         t_setup = time.perf_counter() - t0
         info = h.info
         h.solve_pairs(src, dst)
@@ -69,7 +76,8 @@ def main():
             ref = R
         calls = max(st["cg_spmv_calls"], 1)
         bw = np.mean(np.abs(A.indices - np.repeat(np.arange(m), np.diff(A.indptr))))
-        print(json.dumps({"variant": name, "n": int(m), "nnz": int(A.nnz), "mean_abs_col_minus_row": float(bw),
+        print(json.dumps({"variant": name, "rep": rep_no, "reordered": info["reordered"], "reorder_ms": info["reorder_ms"],
+                          "span_before": info["span_before"], "span_after": info["span_after"], "n": int(m), "nnz": int(A.nnz), "mean_abs_col_minus_row": float(bw),
                           "host_rcm_s": t_rcm if "Cuthill" in name else None, "levels": info["levels"],
                           "level_n": info["level_n"], "operator_complexity": info["operator_complexity"],
                           "setup_wall_s": t_setup, "setup_device_s": info["setup_ms"] / 1e3, "iters_mean": st["total_iters"] / 16.0,
