@@ -91,7 +91,8 @@ struct Knobs {
                                   // passes against 111.7 - 113.7 fused (512 / 256 threads): half the bytes per entry, the same
                                   // LDS traffic and barriers
   int fused_seg = 64;             // coarse columns per tile of that pass (restrict_seg, when given, sets both)
-  int fused_level1 = 0;           // lattice V(2,2) levels: x = S b and b_c = Q2' b in one pass over b (1 on, -1 off, 0 = fp64 only)
+  int fused_level1 = 0;           // lattice V(2,2) levels: 1 = x = S b and b_c = Q2' b in one pass over b, 2 = also out = x + S (b - A x) + Q2 x_c in one
+                                  // chained pass, -1 = four passes, 0 = per precision (pcg.h)
   bool sparse_init = true;        // fused path, pair solves: r0 = e_dst - e_src is never stored (PcgParams::pair_src, pcg.h)
   int64_t collapse_min = -1;      // < 0: the default rule of pcg.h
   bool longrow = true, narrow_tile = false;

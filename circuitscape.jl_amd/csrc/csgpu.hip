@@ -79,7 +79,7 @@ inline Knobs knobs_from_opts(const csgpu_opts& o) {
   k.recompute_ap = flag(o.recompute_ap, true);
   k.fused_restrict = o.fused_restrict > 0 ? 1 : (o.fused_restrict < 0 ? -1 : 0);
   if (o.sparse_init != 0) k.sparse_init = o.sparse_init > 0;
-  k.fused_level1 = o.fused_level1 > 0 ? 1 : (o.fused_level1 < 0 ? -1 : 0);
+  k.fused_level1 = o.fused_level1 > 0 ? std::min(o.fused_level1, 2) : (o.fused_level1 < 0 ? -1 : 0);
   k.longrow = flag(o.longrow, true);
   k.narrow_tile = o.narrow_tile > 0;
   if (o.spmv_grid_cap != 0) k.spmv_grid_cap = std::max(o.spmv_grid_cap, 0);
@@ -142,7 +142,7 @@ inline Knobs knobs_from_opts(const csgpu_opts& o) {
   if (on("NO_RECOMPUTE")) k.recompute_ap = false;
   num("FUSED_RESTRICT", [&](double v) { k.fused_restrict = v > 0 ? 1 : -1; });
   num("SPARSE_INIT", [&](double v) { k.sparse_init = v > 0; });
-  num("FUSED_LEVEL1", [&](double v) { k.fused_level1 = v > 0 ? 1 : -1; });
+  num("FUSED_LEVEL1", [&](double v) { k.fused_level1 = v > 0 ? (v >= 2 ? 2 : 1) : -1; });
   num("COLLAPSE_MIN", [&](double v) { k.collapse_min = (int64_t)v; });
   if (on("NO_LONGROW")) k.longrow = false;
   if (on("NARROW_TILE")) k.narrow_tile = true;
@@ -2480,7 +2480,7 @@ struct Solver : ISolver {
     info->expander_probe_hit = H.expander_probe_hit ? 1 : 0;
     info->fused_restrict_solves = H.fused_restrict_solves;
     info->virtual_rhs_solves = H.virtual_rhs_solves;
-    info->reserved_info3 = 0;
+    info->chained_level1_cycles = H.chained_level1_cycles;
     info->reordered = reordered ? 1 : 0;
     info->reorder_ms = reorder_ms;
     info->span_before = span_before;

@@ -66,6 +66,18 @@ inline bool fused_restrict_wanted() {
   return f > 0 || (f == 0 && sizeof(T) == 8);
 }
 
+// Knobs::fused_level1 = 0 resolved for the back half of a lattice V(2,2) level in precision T: the chained pass (stencil.h)
+// is the default where an A/B on the device showed it winning: a double-precision hierarchy (10000^2, K = 32: 582.8 -> 569.9 ms
+// of device time per batch, profiles/level1_chain_ab.json). An fp32 hierarchy and single precision have not been timed with
+// it and keep the two launches (build-time A/B knob: -DCSGPU_CHAIN_L1_FP64=0)
+#ifndef CSGPU_CHAIN_L1_FP64
+#define CSGPU_CHAIN_L1_FP64 1
+#endif
+template <class T>
+inline bool chained_level1_default() {
+  return sizeof(T) == 8 && CSGPU_CHAIN_L1_FP64 != 0;
+}
+
 // Optional fusions at level 0 of the V-cycle.
 template <class T>
 struct VcycleFuse {
@@ -310,9 +322,16 @@ inline void vcycle(Hierarchy<T>& H, int l, const T* b, T* out, int nu_pre0, int 
     VcycleFuse<T> cf;
     cf.skip = skip;
     vcycle<T, K>(H, l + 1, bc, xc, nu_pre0, nu_post0, nu_coarse, st, &cf);
+    // out = x + S (b - A x) + Q2 x_c (residual, prolongation + post-sweeps): one chained pass that keeps t = b - A x on chip
+    // (stencil.h; fused_level1 = 2), or two launches with t stored
+    if ((f1 >= 2 || (f1 == 0 && chained_level1_default<T>())) &&
+        dia_chain_product<T, K>(L.Adia, L.Sdia, L.Ql, b, (const T*)cur, (const T*)xc, out, skip, st)) {
+      ++H.chained_level1_cycles;
+      return;
+    }
     dia_apply<T, K>(L.Adia, (const T*)cur, oth, b, skip, st);       // t = b - A x
     dia_sq_product<T, K>(L.Sdia, L.Ql, (const T*)oth, (const T*)xc, out, (double*)nullptr, skip, st, (const T*)cur);
-    return;                                                         // out = x + S t + Q2 x_c (prolongation + post-sweeps)
+    return;                                                         // out = x + S t + Q2 x_c
   }
   // pre-smoothing (first sweep from x = 0 is a scaling)
   if (nu_pre >= 1) {
@@ -876,10 +895,17 @@ inline PcgBatchResult pcg_solve(const Csr<T>& A, Hierarchy<TP>& H, PcgWork<T, TP
   int criterion = crit0;  // switches to the true residual for the polishing phase (below)
   // one PCG iteration as a sequence of launches on `st` (no host interaction: this is what gets captured)
   //   p = z + beta p ; Ap = A p, p'Ap ; alpha ; r -= alpha Ap, x += alpha p ; z = M^-1 r, r'z ; beta, stopping rule
+  // The first product of a batch on the lattice path: beta = 0 for every column (the init call above), so the kernel takes
+  // p = z and is not handed the old search direction at all -- a third of the launch's vector traffic, once per batch. That
+  // launch (and its iteration's residual update) stays out of the timed set: cg_spmv_ms / cg_spmv_bytes describe launches of
+  // ONE size.
+  bool first_product = use_dia;
   auto iteration = [&](bool time_it) {
-    const TP* pin = pbuf[parity];
+    const bool short_first = first_product;
+    first_product = false;
+    const TP* pin = short_first ? (const TP*)nullptr : (const TP*)pbuf[parity];
     TP* pcur = use_dia ? pbuf[parity ^ 1] : pbuf[parity];
-    time_it = time_it && timed < max_timed;
+    time_it = time_it && timed < max_timed && !short_first;
     const int tslot = timed;
     auto ev_begin = [&]() {
       if (!time_it) return;
@@ -1185,7 +1211,8 @@ inline PcgBatchResult pcg_solve(const Csr<T>& A, Hierarchy<TP>& H, PcgWork<T, TP
   // launches enqueued after every column had converged return immediately (device flag): leave them out of the average
   int real_its = 0;
   for (int c = 0; c < ncols_active && c < kMaxK; ++c) real_its = std::max(real_its, res.s.iters[c]);
-  const int counted = std::min(timed, real_its);
+  // (on the lattice path the timed launches are those of iterations 1, 2, ...: the first one is shorter, see `iteration`)
+  const int counted = std::min(timed, std::max(real_its - (use_dia ? 1 : 0), 0));
   for (int t = 0; t < counted; ++t) {
     float m2 = 0;
     CS_HIP(hipEventElapsedTime(&m2, W.ev[2 * t], W.ev[2 * t + 1]));

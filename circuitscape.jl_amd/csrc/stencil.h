@@ -156,7 +156,8 @@ struct DiaArgs {
   const T* rows;
   const CgScalars* S;      // beta[c], all_done (may be null: beta = `beta0` for every column, never skipped)
   const XT* z;             // FUSE: p = z + beta * pin; otherwise pin is the input vector and z is unused
-  const XT* pin;
+  const XT* pin;           // DIA_CG only: may be null -- the first product of a batch, beta = 0 for every column: p = z and the
+                           // old search direction is not read at all (block-uniform test, same bits)
   XT* pout;                // FUSE: new search direction (must not alias pin)
   T* y;                    // A p
   double* partials;        // [gridDim.x][K] partials of p'(A p)
@@ -278,6 +279,7 @@ __global__ __launch_bounds__(256, ((MODE == DIA_CG && K >= 8) ? 4 : ((MODE == DI
     T mr[MU];
     T qr[SQ ? QU : 1];
     XV xcr;
+    const bool have_pin = !FUSE || a.pin != nullptr;  // (block-uniform)
     YV r_pre;               // DIA_RUPD: the residual entries of the NEXT column, in flight one step ahead like the vector loads
     int pend_c = -1, next_c = 0;
     auto load_r = [&](int jc) {
@@ -311,7 +313,7 @@ __global__ __launch_bounds__(256, ((MODE == DIA_CG && K >= 8) ? 4 : ((MODE == DI
         if (id >= 0 && id < a.n) {
           const size_t e = (size_t)id * K + c0;
           if (SYNTH) xr = synth(id);
-          else xr = *reinterpret_cast<const XV*>(a.pin + e);
+          else if (have_pin) xr = *reinterpret_cast<const XV*>(a.pin + e);
           if (FUSE) zr = dia_load(reinterpret_cast<const XV*>(a.z + e));
         }
       }
@@ -325,7 +327,7 @@ __global__ __launch_bounds__(256, ((MODE == DIA_CG && K >= 8) ? 4 : ((MODE == DI
         if (id >= 0 && id < a.n) {
           const size_t e = (size_t)id * K + c0;  // (tid < 2 LPR: tid % LPR is the lane's own column slice)
           if (SYNTH) xh = synth(id);
-          else xh = *reinterpret_cast<const XV*>(a.pin + e);
+          else if (have_pin) xh = *reinterpret_cast<const XV*>(a.pin + e);
           if (FUSE) zh = *reinterpret_cast<const XV*>(a.z + e);
         }
       }
@@ -351,12 +353,12 @@ __global__ __launch_bounds__(256, ((MODE == DIA_CG && K >= 8) ? 4 : ((MODE == DI
         XV v;
 #pragma unroll
         // (beta == 0: the first step of a column -- p = z exactly, whatever the old p holds; same bits as the fma otherwise)
-        for (int q = 0; q < CPL; ++q) v.e[q] = beta[q] == T(0) ? zr.e[q] : (XT)fma(beta[q], (T)xr.e[q], (T)zr.e[q]);
+        for (int q = 0; q < CPL; ++q) v.e[q] = (beta[q] == T(0) || !have_pin) ? zr.e[q] : (XT)fma(beta[q], (T)xr.e[q], (T)zr.e[q]);
         const int64_t id = (int64_t)jc * a.R + i0 + t;
         if (jc >= j0 && jc < j1 && row_on && id < a.n) dia_store(reinterpret_cast<XV*>(a.pout + (size_t)id * K + c0), v);
         xr = v;
 #pragma unroll
-        for (int q = 0; q < CPL; ++q) xh.e[q] = beta[q] == T(0) ? zh.e[q] : (XT)fma(beta[q], (T)xh.e[q], (T)zh.e[q]);
+        for (int q = 0; q < CPL; ++q) xh.e[q] = (beta[q] == T(0) || !have_pin) ? zh.e[q] : (XT)fma(beta[q], (T)xh.e[q], (T)zh.e[q]);
       }
       s_x[slot][(t + 1) * LPR + lq] = xr;
       if (tid < 2 * LPR) s_x[slot][(tid < LPR ? 0 : TI + 1) * LPR + lq] = xh;
@@ -555,6 +557,7 @@ inline int dia_grid(const Dia<T>& D) {
 }
 
 // p_out = z + beta p_in ; y = A p_out ; partials of p_out' y   (beta and the skip flag from the CG scalars S)
+// pin == nullptr: the first product of a batch (beta = 0 for every column), p_out = z without a read of the old direction
 template <class T, class XT, int K>
 inline void dia_cg_product(const Dia<T>& D, const CgScalars* S, const XT* z, const XT* pin, XT* pout, T* y,
                            double* partials, hipStream_t st, const double* beta_dev = nullptr) {
@@ -597,6 +600,7 @@ inline void dia_residual_update(const Dia<T>& D, const CgScalars* S, const XT* p
   a.rows = D.data();
   a.S = S;
   a.z = nullptr;
+  CS_REQUIRE(p != nullptr, CSGPU_INTERNAL, "lattice residual update without a search direction");
   a.pin = p;
   a.pout = nullptr;
   a.y = nullptr;
@@ -628,6 +632,7 @@ inline void dia_sq_product(const Dia<T>& Sd, const LatticeQ<T>& Q, const T* b, c
   a.rows = Sd.data();
   a.S = nullptr;
   a.z = nullptr;
+  CS_REQUIRE(b != nullptr || psrc != nullptr, CSGPU_INTERNAL, "lattice second product without an input vector");
   a.pin = b;
   a.pout = nullptr;
   a.y = out;
@@ -668,6 +673,7 @@ inline void dia_apply(const Dia<T>& D, const T* x, T* y, const T* bsub, const in
   a.rows = D.data();
   a.S = nullptr;
   a.z = nullptr;
+  CS_REQUIRE(x != nullptr, CSGPU_INTERNAL, "lattice product without an input vector");
   a.pin = x;
   a.pout = nullptr;
   a.y = y;
@@ -682,6 +688,320 @@ inline void dia_apply(const Dia<T>& D, const T* x, T* y, const T* bsub, const in
   a.xsol = nullptr;
   a.bsub = bsub;
   hipLaunchKernelGGL((dia_cg_kernel<T, T, K, DIA_PLAIN>), dim3(grid), dim3(256), 0, st, a);
+}
+
+// ---- second half of a lattice V(2,2) level in ONE marching pass (pcg.h, Knobs::fused_level1 = 2) -------------------------
+// out = x + S (b - A x) + Q xc: what dia_apply(A, x, t, bsub = b) followed by dia_sq_product(S, Q, t, xc, out, xadd = x) compute,
+// without t ever reaching memory and with x read once (3 vector passes instead of 6). Every entry gets the arithmetic of the
+// two launches bit for bit: t = b - (nine-term chain of dia_cg_kernel), then the S chain, the nine Q fmas in DIA_SQ's
+// (dj, di) order, then + x.
+//
+// Shape: the 256-thread tile of dia_cg_kernel. The TI lanes of a slice stage TI consecutive node ids of a raster column and
+// ALL of them compute t (from x staged one id further out on both sides, s_x rows -1 .. TI); the inner TI - 2 own an entry of
+// out, so a workgroup recomputes t on the one-cell ring around its cells -- from the same linear staging, hence with the
+// neighbouring workgroup's bits. Ids outside [0, n) give t = 0, like a stored t read out of range. Per step the kernel
+// stores the bundle loaded one step ago (x of column j+2, b and the rows of A of column j+1, the rows of S and Q of column j),
+// issues the loads of the next one, computes t of column j+1 into the LDS ring and then out of column j.
+template <class T>
+struct DiaChainArgs {
+  int64_t n;
+  int R, C;
+  int nstrips, nseg, seg;  // tiles: nstrips strips of TI - 2 rows x nseg segments of seg raster columns
+  const T* arows;          // lattice form of A
+  const T* srows;          // lattice form of S
+  const T* qell;           // index-free Q, [n][9]
+  int Rc, Cc;
+  const T* b;
+  const T* x;
+  const T* xc;             // coarse solution, interleaved [Rc*Cc][K]
+  T* out;                  // must not alias b or x
+  const int* skip;
+};
+
+template <class T, int K>
+constexpr bool dia_chain_fits() {
+  return K >= 16 && DiaShape<T, T, K>::TI >= 8;
+}
+
+template <class T, int K>
+__global__ __launch_bounds__(256) void dia_chain_kernel(DiaChainArgs<T> a) {
+  typedef DiaShape<T, T, K> SH;
+  constexpr int CPL = SH::CPL, LPR = SH::LPR, TI = SH::TI, MELEMS = SH::MELEMS, MU = SH::MU;
+  constexpr int QELEMS = SH::QELEMS, QU = SH::QU, CR = SH::CR;
+  constexpr int TO = TI - 2;  // rows owned
+  typedef SpmvVec<T, CPL> XV;
+  static_assert(CR * LPR <= 256, "one lane per staged coarse entry");
+  __shared__ XV s_x[2][(TI + 2) * LPR];   // x of the newest column, lane rows -1 .. TI (older columns live in the window)
+  __shared__ XV s_t[2][(TI + 2) * LPR];   // t of the newest column, lane rows 0 .. TI-1 at index row + 1
+  __shared__ T s_ma[4][MELEMS];           // rows of A, ring over raster columns, lane rows -1 .. TI
+  __shared__ T s_ms[4][MELEMS];           // rows of S
+  __shared__ T s_q[2][QELEMS];            // Q of the column whose out is taken, lane rows 0 .. TI-1
+  __shared__ XV s_xc[4][CR * LPR];        // coarse columns J-1 .. J+2 (ring), rows Ilo .. Ilo+CR-1
+  if (a.skip && *a.skip) return;
+  const int tid = threadIdx.x;
+  const int t = tid / LPR;   // lane row: raster row i0 - 1 + t of the strip (linear in the node id)
+  const int lq = tid % LPR;
+  const int c0 = lq * CPL;
+  const int ntiles = a.nstrips * a.nseg;
+  // XCD-aware tile walk (see dia_cg_kernel)
+  int t_first = blockIdx.x, t_last = ntiles, t_step = gridDim.x;
+  if ((gridDim.x & 7) == 0) {
+    const int xcd = blockIdx.x & 7, chunk = (ntiles + 7) >> 3;
+    t_first = xcd * chunk + (blockIdx.x >> 3);
+    t_last = min(ntiles, (xcd + 1) * chunk);
+    t_step = gridDim.x >> 3;
+  }
+  for (int tile = t_first; tile < t_last; tile += t_step) {
+    const int si = tile % a.nstrips, sj = tile / a.nstrips;
+    const int i0 = si * TO;  // first raster row owned
+    const int j0 = sj * a.seg, j1 = min(a.C, j0 + a.seg);
+    const bool own = t >= 1 && t <= TO && i0 - 1 + t < a.R;
+    const int Ilo = min(i0 / 3, a.Rc - 1) - 1;
+    const int crow = min(max(i0 - 1 + t, 0) / 3, a.Rc - 1) - Ilo;
+    XV xr, xh, br, xcr;
+    T mar[MU], msr[MU], qr[QU];
+    int pend_c = -1, next_c = 0;
+    auto load_coarse = [&](int Jc) {
+#pragma unroll
+      for (int q = 0; q < CPL; ++q) xcr.e[q] = T(0);
+      if (tid < CR * LPR) {
+        const int Ic = Ilo + tid / LPR;
+        if (Jc >= 0 && Jc < a.Cc && Ic >= 0 && Ic < a.Rc)
+          xcr = *reinterpret_cast<const XV*>(a.xc + ((size_t)Jc * a.Rc + Ic) * K + (tid % LPR) * CPL);
+      }
+    };
+    auto store_coarse = [&](int Jc) {
+      if (tid < CR * LPR) s_xc[Jc & 3][tid] = xcr;
+    };
+    // bundle jc: x of raster column jc, b and the rows of A of column jc-1, the rows of S and Q of column jc-2
+    auto load_bundle = [&](int jc) {
+      const int64_t base = (int64_t)jc * a.R + i0 - 2;  // node id of lane row -1 in column jc; ids outside [0, n) read as zero
+#pragma unroll
+      for (int q = 0; q < CPL; ++q) {
+        xr.e[q] = T(0);
+        br.e[q] = T(0);
+      }
+      {
+        const int64_t id = base + 1 + t;
+        if (id >= 0 && id < a.n) xr = *reinterpret_cast<const XV*>(a.x + (size_t)id * K + c0);
+        const int64_t idb = id - a.R;
+        if (jc - 1 >= j0 - 1 && jc - 1 <= j1 && idb >= 0 && idb < a.n)
+          br = dia_load(reinterpret_cast<const XV*>(a.b + (size_t)idb * K + c0));
+      }
+      if (tid < 2 * LPR) {  // lane rows -1 (lanes 0..LPR-1) and TI (lanes LPR..2LPR-1)
+        const int64_t id = base + (tid < LPR ? 0 : TI + 1);
+#pragma unroll
+        for (int q = 0; q < CPL; ++q) xh.e[q] = T(0);
+        if (id >= 0 && id < a.n) xh = *reinterpret_cast<const XV*>(a.x + (size_t)id * K + c0);
+      }
+      const int64_t ba = (base - a.R) * 5, bs = (base - 2 * (int64_t)a.R) * 5;
+#pragma unroll
+      for (int u = 0; u < MU; ++u) {
+        const int e = tid + u * 256;
+        const int64_t ga = ba + e, gs = bs + e;
+        mar[u] = (e < MELEMS && ga >= 0 && ga < a.n * 5) ? a.arows[ga] : T(0);
+        msr[u] = (jc - 2 >= j0 - 1 && e < MELEMS && gs >= 0 && gs < a.n * 5) ? a.srows[gs] : T(0);
+      }
+      const int64_t qb = (base + 1 - 2 * (int64_t)a.R) * 9;
+#pragma unroll
+      for (int u = 0; u < QU; ++u) {
+        const int e = tid + u * 256;
+        const int64_t g = qb + e;
+        qr[u] = (jc - 2 >= j0 && e < QELEMS && g >= 0 && g < a.n * 9) ? a.qell[g] : T(0);
+      }
+    };
+    auto store_bundle = [&](int jc) {
+      s_x[jc & 1][(t + 1) * LPR + lq] = xr;
+      if (tid < 2 * LPR) s_x[jc & 1][(tid < LPR ? 0 : TI + 1) * LPR + lq] = xh;
+#pragma unroll
+      for (int u = 0; u < MU; ++u) {
+        const int e = tid + u * 256;
+        if (e < MELEMS) {
+          s_ma[(jc - 1) & 3][e] = mar[u];
+          s_ms[(jc - 2) & 3][e] = msr[u];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < QU; ++u) {
+        const int e = tid + u * 256;
+        if (e < QELEMS) s_q[jc & 1][e] = qr[u];
+      }
+    };
+    __syncthreads();  // previous tile finished with the rings
+    load_bundle(j0 - 2);
+    {  // coarse columns J(j0)-1 .. J(j0)+2 up front; later ones one per step, two steps ahead of their use
+      const int Jb = min(j0 / 3, a.Cc - 1);
+      for (int d = -1; d <= 2; ++d) {
+        load_coarse(Jb + d);
+        store_coarse(Jb + d);
+      }
+      next_c = Jb + 3;
+    }
+    // sliding windows: xw[dj][di] = x(lane row t-1+di, raster column j+dj), tw[dj][di] = t(lane row t-1+di, column j-1+dj)
+    XV xw[3][3], tw[3][3];
+#pragma unroll
+    for (int dj = 0; dj < 3; ++dj)
+#pragma unroll
+      for (int di = 0; di < 3; ++di)
+#pragma unroll
+        for (int q = 0; q < CPL; ++q) xw[dj][di].e[q] = tw[dj][di].e[q] = T(0);
+    // steps j0-4 .. j0-1 fill the windows (t of column j0-1 is taken at step j0-2), steps j0 .. j1-1 write out
+    for (int j = j0 - 4; j < j1; ++j) {
+      store_bundle(j + 2);  // the bundle loaded one step ago
+      const XV b_cur = br;  // b of column j+1
+      if (pend_c >= 0) {
+        store_coarse(pend_c);
+        pend_c = -1;
+      }
+      if (j + 3 <= j1 + 1) load_bundle(j + 3);  // next one in flight while this step computes
+      if (j >= j0) {
+        const int need = min((j + 2) / 3, a.Cc - 1) + 1;  // last coarse column read two steps from now
+        if (need >= next_c) {
+          load_coarse(next_c);
+          pend_c = next_c++;
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int di = 0; di < 3; ++di) {
+        xw[0][di] = xw[1][di];
+        xw[1][di] = xw[2][di];
+        xw[2][di] = s_x[(j + 2) & 1][(t + di) * LPR + lq];
+      }
+      // t = b - A x of column j+1, every lane row
+      XV tv;
+#pragma unroll
+      for (int q = 0; q < CPL; ++q) tv.e[q] = T(0);
+      {
+        const int64_t id = (int64_t)(j + 1) * a.R + i0 - 1 + t;
+        if (j + 1 >= j0 - 1 && id >= 0 && id < a.n) {
+          const T* mc = s_ma[(j + 1) & 3];
+          const T* mp = s_ma[j & 3];
+          const int me = 5 * (t + 1);
+          const T w_mm = mp[me - 5 + 4];
+          const T w_m0 = mp[me + 3];
+          const T w_mp = mp[me + 5 + 2];
+          const T w_0m = mc[me - 5 + 1];
+          const T w_00 = mc[me + 0];
+          const T w_0p = mc[me + 1];
+          const T w_pm = mc[me + 2];
+          const T w_p0 = mc[me + 3];
+          const T w_pp = mc[me + 4];
+#pragma unroll
+          for (int q = 0; q < CPL; ++q) {
+            T s = w_mm * xw[0][0].e[q];
+            s = fma(w_m0, xw[0][1].e[q], s);
+            s = fma(w_mp, xw[0][2].e[q], s);
+            s = fma(w_0m, xw[1][0].e[q], s);
+            s = fma(w_00, xw[1][1].e[q], s);
+            s = fma(w_0p, xw[1][2].e[q], s);
+            s = fma(w_pm, xw[2][0].e[q], s);
+            s = fma(w_p0, xw[2][1].e[q], s);
+            s = fma(w_pp, xw[2][2].e[q], s);
+            tv.e[q] = b_cur.e[q] - s;
+          }
+        }
+      }
+      s_t[(j + 1) & 1][(t + 1) * LPR + lq] = tv;
+      __syncthreads();
+#pragma unroll
+      for (int di = 0; di < 3; ++di) {
+        tw[0][di] = tw[1][di];
+        tw[1][di] = tw[2][di];
+      }
+      tw[2][0] = s_t[(j + 1) & 1][t * LPR + lq];  // (lane rows -1 and TI are never written: read by lanes that own nothing)
+      tw[2][1] = tv;
+      tw[2][2] = s_t[(j + 1) & 1][(t + 2) * LPR + lq];
+      if (j >= j0 && own) {
+        const T* mc = s_ms[j & 3];
+        const T* mp = s_ms[(j - 1) & 3];
+        const int me = 5 * (t + 1);
+        const T w_mm = mp[me - 5 + 4];
+        const T w_m0 = mp[me + 3];
+        const T w_mp = mp[me + 5 + 2];
+        const T w_0m = mc[me - 5 + 1];
+        const T w_00 = mc[me + 0];
+        const T w_0p = mc[me + 1];
+        const T w_pm = mc[me + 2];
+        const T w_p0 = mc[me + 3];
+        const T w_pp = mc[me + 4];
+        XV out;
+#pragma unroll
+        for (int q = 0; q < CPL; ++q) {
+          T s = w_mm * tw[0][0].e[q];
+          s = fma(w_m0, tw[0][1].e[q], s);
+          s = fma(w_mp, tw[0][2].e[q], s);
+          s = fma(w_0m, tw[1][0].e[q], s);
+          s = fma(w_00, tw[1][1].e[q], s);
+          s = fma(w_0p, tw[1][2].e[q], s);
+          s = fma(w_pm, tw[2][0].e[q], s);
+          s = fma(w_p0, tw[2][1].e[q], s);
+          s = fma(w_pp, tw[2][2].e[q], s);
+          out.e[q] = s;
+        }
+        const T* qrow = s_q[j & 1] + 9 * t;
+        const int Jj = min(j / 3, a.Cc - 1);
+#pragma unroll 1
+        for (int dj = 0; dj < 3; ++dj) {
+          const XV* xcol = s_xc[(Jj + dj - 1) & 3];
+#pragma unroll
+          for (int di = 0; di < 3; ++di) {
+            const T w = qrow[dj * 3 + di];
+            const XV xv = xcol[(crow + di - 1) * LPR + lq];
+#pragma unroll
+            for (int q = 0; q < CPL; ++q) out.e[q] = fma(w, xv.e[q], out.e[q]);
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < CPL; ++q) out.e[q] += xw[0][1].e[q];  // + x (the two-launch form reads it back as xadd)
+        const int64_t id = (int64_t)j * a.R + i0 - 1 + t;
+        dia_store(reinterpret_cast<XV*>(a.out + (size_t)id * K + c0), out);
+      }
+    }
+  }
+}
+
+template <class T, int K>
+inline void dia_chain_tiling(const Dia<T>& D, int& nstrips, int& nseg, int& seg, int& grid) {
+  const int C = (int)(D.n / D.R);
+  seg = std::min(dia_seg(K), std::max(C, 1));
+  nstrips = ceil_div(D.R, DiaShape<T, T, K>::TI - 2);
+  nseg = ceil_div(C, seg);
+  int64_t g = (int64_t)nstrips * nseg;
+  const int64_t cap = std::max(1024, spmv_grid_cap());
+  if (g > cap) g = cap;
+  if (g >= 64) g &= ~(int64_t)7;
+  grid = (int)std::max<int64_t>(g, 1);
+}
+
+// out = x + S (b - A x) + Q xc in one pass; false (nothing launched) where the kernel does not fit
+template <class T, int K>
+inline bool dia_chain_product(const Dia<T>& Ad, const Dia<T>& Sd, const LatticeQ<T>& Q, const T* b, const T* x, const T* xc,
+                              T* out, const int* skip, hipStream_t st) {
+  if constexpr (dia_chain_fits<T, K>()) {
+    if (Ad.n != Sd.n || Ad.R != Sd.R || Q.R != Sd.R || (int64_t)Q.R * Q.C != Sd.n) return false;
+    CS_REQUIRE(b && x && xc && out && out != b && out != x, CSGPU_INTERNAL, "chained level-1 pass: bad vectors");
+    DiaChainArgs<T> a;
+    a.n = Sd.n;
+    a.R = Sd.R;
+    a.C = (int)(Sd.n / Sd.R);
+    int grid;
+    dia_chain_tiling<T, K>(Sd, a.nstrips, a.nseg, a.seg, grid);
+    a.arows = Ad.data();
+    a.srows = Sd.data();
+    a.qell = Q.data();
+    a.Rc = Q.Rc;
+    a.Cc = Q.Cc;
+    a.b = b;
+    a.x = x;
+    a.xc = xc;
+    a.out = out;
+    a.skip = skip;
+    hipLaunchKernelGGL((dia_chain_kernel<T, K>), dim3(grid), dim3(256), 0, st, a);
+    return true;
+  } else {
+    return false;
+  }
 }
 
 // Lattice form of S = 2 w D^-1 - w D^-1 A w D^-1 (w = damped-Jacobi weight) from the lattice form of A (precision U,

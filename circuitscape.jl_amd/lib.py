@@ -78,7 +78,7 @@ class Info(ctypes.Structure):
         ("batch_width", ctypes.c_int32), ("stream_mode", ctypes.c_int32), ("tail_first_level", ctypes.c_int32),
         ("last_level_sweeps", ctypes.c_int32), ("coarse_chebyshev", ctypes.c_int32), ("cellspace", ctypes.c_int32),
         ("poly_lattice", ctypes.c_int32), ("enrich_on", ctypes.c_int32), ("enrich_tau", ctypes.c_double),
-        ("expander_probe_hit", ctypes.c_int32), ("fused_restrict_solves", ctypes.c_int32), ("virtual_rhs_solves", ctypes.c_int32), ("reserved_info3", ctypes.c_int32),
+        ("expander_probe_hit", ctypes.c_int32), ("fused_restrict_solves", ctypes.c_int32), ("virtual_rhs_solves", ctypes.c_int32), ("chained_level1_cycles", ctypes.c_int32),
         ("reorder_ms", ctypes.c_double), ("span_before", ctypes.c_double), ("span_after", ctypes.c_double),
     ]
 

@@ -247,8 +247,13 @@ typedef struct csgpu_opts {
                                  never stored -- the first restriction scatters <= 18 entries per column, the first second
                                  product and the first residual update synthesise it (three passes over n x batch values and
                                  the clearing of r saved per batch, same bits); -1 = r0 written and read like any residual */
-  int32_t fused_level1;       /* lattice V(2,2) levels (level 1 of a full raster): 1 = x = S b and b_c = Q2' b in one marching pass
-                                 over b, -1 = two passes, 0 = fused in double precision; same bits either way */
+  int32_t fused_level1;       /* lattice V(2,2) levels (level 1 of a full raster): 1 = the front half, x = S b and b_c = Q2' b, in one
+                                 marching pass over b, the back half in two (t = b - A x stored, then out = x + S t + Q2 x_c);
+                                 2 = the front half in one pass and the back half in one CHAINED pass that keeps t on chip
+                                 (three vector passes instead of six; batches of 16 / 32 columns, otherwise as 1); -1 = four
+                                 passes; 0 = library default: 2 in a double-precision hierarchy (-2.2 % of a batch at 10000^2), four
+                                 passes in a single-precision one (the chained pass has not been timed there); same bits
+                                 whichever runs (csgpu_info.chained_level1_cycles tells) */
   int64_t stream_min;         /* vector elements n * batch from which streaming is considered, 0 = 2^25 */
   int64_t host_stream_block;  /* csgpu_setup: stream the host matrix in blocks of at most this many entries (test / tuning);
                                  0 = only matrices with >= 2^31 stored entries, in blocks of 2^28 */
@@ -309,7 +314,8 @@ typedef struct csgpu_info {
   int32_t expander_probe_hit;   /* 1 = the expansion probe predicted the expander bail-out and the aggregation was skipped */
   int32_t fused_restrict_solves; /* batches so far whose PCG ran the fused residual update + restriction (csgpu_opts.fused_restrict) */
   int32_t virtual_rhs_solves;    /* ... of which the right-hand side was never stored (csgpu_opts.sparse_init) */
-  int32_t reserved_info3;
+  int32_t chained_level1_cycles; /* V-cycles enqueued so far whose level 1 ran the chained residual + post-smoothing pass
+                                    (csgpu_opts.fused_level1 = 2) */
   double reorder_ms;            /* csgpu_opts.reorder: HIP-event time of the ordering and of the permutation of the matrix (incl. the
                                    lattice / expansion checks that decide whether to reorder); INCLUDED in setup_ms */
   double span_before;           /* reordered handles: mean |col - row| / n over the stored entries of the matrix as given ... */
