@@ -86,7 +86,9 @@ struct Knobs {
   bool fixed_k = false;           // every batch of a call at the call's width (round-5 behaviour)
   bool recompute_ap = true;       // residual update recomputes A p from the lattice form instead of storing it
   int fused_restrict = 0;         // residual update and the V-cycle's restriction in one marching pass (lattice.h): 1 on, -1 off,
-                                  // 0 = on in double precision only. Measured at 10000^2, K = 32:
+                                  // 0 = on in double precision only, and only for resistance-only pair solves: a solve that
+                                  // carries the solution takes the pass (with x += alpha p in it, W.r2 on top of x, b, A p)
+                                  // with 1 alone (pcg.h). Measured at 10000^2, K = 32:
                                   // fp64 45.2 - 46.8 -> 49.1 - 49.4 pair-solves/s; single precision 117.5 - 119.4 with two
                                   // passes against 111.7 - 113.7 fused (512 / 256 threads): half the bytes per entry, the same
                                   // LDS traffic and barriers

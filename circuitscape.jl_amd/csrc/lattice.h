@@ -287,6 +287,9 @@ struct RupdRestrictArgs {
   // APPLY form of the kernel (a lattice V(2,2) level, pcg.h): r_out = D p and bc = Q^T p in one pass over p -- `rows` is the
   // lattice form of D (the level's two-sweep operator S), r_in / S / partials are unused, `skip` is the cycle's skip flag
   const int* skip = nullptr;
+  // XUP form (a solve that carries the whole solution, pcg.h): xsol += alpha p at the OWNED entries, the arithmetic of the
+  // two-pass update (stencil.h). Never with APPLY, restart / src / dst or isrc / idst (such solves store b).
+  T* xsol = nullptr;
 };
 
 template <class T, int K, int NT>
@@ -306,8 +309,9 @@ struct RupdRestrictShape {
                                       (size_t)FR * 9 * sizeof(T) + (size_t)(NT / 64) * K * sizeof(double);
 };
 
-template <class T, int K, int NT, bool APPLY = false>
+template <class T, int K, int NT, bool APPLY = false, bool XUP = false>
 __global__ __launch_bounds__(NT) void lattice_rupd_restrict_kernel(RupdRestrictArgs<T> a) {
+  static_assert(!(APPLY && XUP), "the solution update belongs to the residual update");
   typedef RupdRestrictShape<T, K, NT> SH;
   constexpr int CPL = SH::CPL, LPR = SH::LPR, TIC = SH::TIC, FR = SH::FR, PR = SH::PR, BU = SH::BU, PU = SH::PU, MU = SH::MU,
                 QU = SH::QU;
@@ -331,12 +335,12 @@ __global__ __launch_bounds__(NT) void lattice_rupd_restrict_kernel(RupdRestrictA
 #pragma unroll
   for (int qq = 0; qq < CPL; ++qq) {
     dot_acc[qq] = 0.0;
-    fresh[qq] = !APPLY && a.restart && a.restart[c0 + qq] != 0;
+    fresh[qq] = !APPLY && !XUP && a.restart && a.restart[c0 + qq] != 0;  // (XUP: the launcher asserts there is none)
     nsrc[qq] = fresh[qq] ? a.src[c0 + qq] : -1;
     ndst[qq] = fresh[qq] ? a.dst[c0 + qq] : -1;
     if (nsrc[qq] == ndst[qq]) nsrc[qq] = ndst[qq] = -1;
   }
-  const bool synth_in = !APPLY && a.isrc != nullptr;
+  const bool synth_in = !APPLY && !XUP && a.isrc != nullptr;
   int64_t is_[CPL], id_[CPL];
 #pragma unroll
   for (int qq = 0; qq < CPL; ++qq) {
@@ -378,6 +382,7 @@ __global__ __launch_bounds__(NT) void lattice_rupd_restrict_kernel(RupdRestrictA
     XV preg[PU];
     T mreg[MU];
     XV rreg[BU];
+    XV xreg[XUP ? BU : 1];  // (XUP: the owned entries of the solution, in flight with r)
     T qreg[QU];
     auto load_pm = [&](int f) {  // column f of p and of the matrix: staged rows f0 - 1 .. f0 + nfr (ids outside [0, n): zero)
       const int64_t base = (int64_t)f * a.R + f0 - 1;
@@ -428,6 +433,15 @@ __global__ __launch_bounds__(NT) void lattice_rupd_restrict_kernel(RupdRestrictA
           }
         }
         rreg[u] = v;
+        if constexpr (XUP) {  // (only what this workgroup owns: halo entries are another workgroup's to read and write)
+          XV xv;
+#pragma unroll
+          for (int qq = 0; qq < CPL; ++qq) xv.e[qq] = T(0);
+          const int fr = f0 + row;
+          if (f >= oc0 && f < oc1 && row < nfr && fr >= o0 && fr < o1)
+            xv = *reinterpret_cast<const XV*>(a.xsol + (size_t)(base + row) * K + c0);
+          xreg[u] = xv;
+        }
       }
 #pragma unroll
       for (int u = 0; u < QU; ++u) {
@@ -462,9 +476,14 @@ __global__ __launch_bounds__(NT) void lattice_rupd_restrict_kernel(RupdRestrictA
       store_pm(sp);  // (the slot column f - 2 had: its last readers passed the second barrier of the previous step)
       load_pm(f + 2);
       XV rv[BU];
+      XV xv[XUP ? BU : 1];
       T qv[QU];
 #pragma unroll
       for (int u = 0; u < BU; ++u) rv[u] = rreg[u];
+      if constexpr (XUP) {
+#pragma unroll
+        for (int u = 0; u < BU; ++u) xv[u] = xreg[u];
+      }
 #pragma unroll
       for (int u = 0; u < QU; ++u) qv[u] = qreg[u];
       load_rq(f + 1);
@@ -538,6 +557,18 @@ __global__ __launch_bounds__(NT) void lattice_rupd_restrict_kernel(RupdRestrictA
             if (fresh[qq]) rn.e[qq] = id == nsrc[qq] ? T(-1) : (id == ndst[qq] ? T(1) : T(0));
           s_b[row * LPR + lq] = APPLY ? ctr[u] : rn;  // (APPLY: the restriction is of the INPUT vector)
           if (owned) dia_store(reinterpret_cast<XV*>(a.r_out + (size_t)id * K + c0), rn);
+          if constexpr (XUP) {
+            if (owned) {
+              // x += alpha p: the expression of the two-pass update (a stopped column has alpha = 0). p at the entry comes
+              // from the ring again rather than from `ctr`: BU vectors fewer live across the third ring column, which is what
+              // keeps the float / K = 16 instantiation out of scratch (256 VGPRs at two waves per SIMD)
+              XV xn;
+              const XV pc = x0[(row + 1) * LPR + lq];
+#pragma unroll
+              for (int qq = 0; qq < CPL; ++qq) xn.e[qq] = fma(alpha[qq], pc.e[qq], xv[u].e[qq]);
+              dia_store(reinterpret_cast<XV*>(a.xsol + (size_t)id * K + c0), xn);
+            }
+          }
         }
       }
 #pragma unroll
@@ -637,7 +668,10 @@ template <class T, int K>
 inline int lattice_rupd_restrict(const Dia<T>& D, const LatticeQ<T>& Q, const CgScalars* S, const T* p, const T* r_in, T* r_out,
                                  T* bc, double* partials, hipStream_t st, const int* restart = nullptr,
                                  const int* src = nullptr, const int* dst = nullptr, const int* isrc = nullptr,
-                                 const int* idst = nullptr, int icols = 0) {
+                                 const int* idst = nullptr, int icols = 0, T* xsol = nullptr) {
+  // (a solve that carries the solution stores b: no streaming restart, no synthesised first residual)
+  CS_REQUIRE(!xsol || (!restart && !src && !dst && !isrc && !idst), CSGPU_INTERNAL,
+             "fused residual update: the solution update takes a stored residual");
   if constexpr (lattice_rupd_restrict_fits<T, K>()) {
     constexpr int NT = kFusedNT;
     RupdRestrictArgs<T> a;
@@ -661,10 +695,14 @@ inline int lattice_rupd_restrict(const Dia<T>& D, const LatticeQ<T>& Q, const Cg
     a.isrc = isrc;
     a.idst = idst;
     a.icols = icols;
-    hipLaunchKernelGGL((lattice_rupd_restrict_kernel<T, K, NT>), dim3(g), dim3(NT), 0, st, a);
+    a.xsol = xsol;
+    if (xsol)
+      hipLaunchKernelGGL((lattice_rupd_restrict_kernel<T, K, NT, false, true>), dim3(g), dim3(NT), 0, st, a);
+    else
+      hipLaunchKernelGGL((lattice_rupd_restrict_kernel<T, K, NT>), dim3(g), dim3(NT), 0, st, a);
     return partials ? g : 0;
   } else {
-    (void)D; (void)Q; (void)S; (void)p; (void)r_in; (void)r_out; (void)bc; (void)partials; (void)st; (void)restart; (void)src; (void)dst; (void)isrc; (void)idst; (void)icols;
+    (void)D; (void)Q; (void)S; (void)p; (void)r_in; (void)r_out; (void)bc; (void)partials; (void)st; (void)restart; (void)src; (void)dst; (void)isrc; (void)idst; (void)icols; (void)xsol;
     return 0;
   }
 }

@@ -483,6 +483,7 @@ struct PcgGraphKey {
   double rtol = 0, atol = 0;
   const void* matrix = nullptr;
   int need_x = 0, nf = 0, parity = 0;
+  int fused = 0;  // the chunk's residual update is the fused pass (a polishing phase continues two-pass in the same buffers)
   // Dirichlet sets of the batch: the list pointers and the launch geometry of the mask kernels are baked into a chunk
   const void* gptr = nullptr;
   const void* gidx = nullptr;
@@ -491,7 +492,7 @@ struct PcgGraphKey {
   bool operator==(const PcgGraphKey& o) const {
     return K == o.K && ncols_active == o.ncols_active && criterion == o.criterion && nu_pre == o.nu_pre &&
            nu_post == o.nu_post && nu_coarse == o.nu_coarse && iters == o.iters && rtol == o.rtol && atol == o.atol &&
-           matrix == o.matrix && need_x == o.need_x && nf == o.nf && parity == o.parity && gptr == o.gptr &&
+           matrix == o.matrix && need_x == o.need_x && nf == o.nf && parity == o.parity && fused == o.fused && gptr == o.gptr &&
            gidx == o.gidx && gtotal == o.gtotal && proj == o.proj;
   }
 };
@@ -516,6 +517,7 @@ struct PcgWork {
   DBuf fnode, xf;             // focal mode (PcgParams::need_x == false): nf node ids, solution values [nf][K] (T)
   int nf = 0;
   bool have_x = false;        // x holds the solution of the last solve (need_x was set)
+  bool r2_oom_said = false;   // (verbose: the two-pass fallback of an x-carrying solve without room for r2 was reported)
   DBuf scalars;               // CgScalars
   DBuf dir_coef;              // [kMaxDirComp][kMaxK] doubles: 1 / G of a Dirichlet-masked solve (DirichletCoarse in pcg_solve)
   DBuf part_a, part_b, part_c;
@@ -737,21 +739,44 @@ inline PcgBatchResult pcg_solve(const Csr<T>& A, Hierarchy<TP>& H, PcgWork<T, TP
   // Fused residual update + restriction (lattice.h, Knobs::fused_restrict): r_new = r - alpha A p and b_c = Q^T r_new in one
   // pass. The residual then ping-pongs between W.r and W.r2 -- `r` / `rp` below are re-pointed after every fused launch and
   // `rsel` (which buffer holds the current residual) is part of the graph key. One precision only (the V-cycle reads r
-  // itself), resistance-only pair solves without masks or projections (which touch r between the update and the cycle). An
+  // itself), solves without masks or projections (which touch r between the update and the cycle). An
   // ENRICHED level takes it when the set-up built W = Q'AE (EN.ntouch > 0): enrich_pre changes r on its halo cells after
   // the pass has restricted it, and enrich_coarse_fix applies the restriction's share of that change to b_c (enrich.h).
+  // A solve that carries the whole solution takes it only when asked to (Knobs::fused_restrict = 1): the pass then also
+  // runs x += alpha p on the cells it owns (the XUP form of the kernel), and W.r2 comes ON TOP of x, b and A p -- the
+  // default leaves such a solve's device memory as it was.
   bool fused_rr = false;
   T* rbuf[2] = {r, nullptr};
   int rsel = 0;
   if constexpr (!MIXED && lattice_rupd_restrict_fits<T, K>()) {
-    fused_rr = fused_restrict_wanted<T>() && recompute && two_product && L0.lattice_two_product() && !need_x && !grounded &&
-               !projected && (!enrich || EN.ntouch > 0) && pp.nu_pre == 1 && pp.nu_post == 1;
+    fused_rr = fused_restrict_wanted<T>() && recompute && two_product && L0.lattice_two_product() &&
+               (!need_x || knobs().fused_restrict > 0) && !grounded && !projected && (!enrich || EN.ntouch > 0) &&
+               pp.nu_pre == 1 && pp.nu_post == 1;
     if (fused_rr) {
       const size_t want = ((size_t)n + (size_t)W.tail) * K * sizeof(T);
       if (W.r2.bytes < want) {
         W.drop_graphs();
-        W.r2.alloc(want);
+        if (need_x) {
+          // the extra n x K buffer of a solve that works without it: out of memory here is no failure of the call
+          try {
+            W.r2.alloc(want);
+          } catch (const Error& e) {
+            if (e.code != CSGPU_OOM) throw;
+            (void)hipGetLastError();
+            W.r2.release();
+            fused_rr = false;
+            if (knobs().verbose && !W.r2_oom_said) {
+              W.r2_oom_said = true;
+              fprintf(stderr, "csgpu: fused residual update + restriction: no memory for the second residual buffer of a "
+                              "solve that carries the solution, two passes instead\n");
+            }
+          }
+        } else {
+          W.r2.alloc(want);
+        }
       }
+    }
+    if (fused_rr) {
       rbuf[1] = dptr<T>(W.r2);
       ++H.fused_restrict_solves;
     }
@@ -958,7 +983,8 @@ inline PcgBatchResult pcg_solve(const Csr<T>& A, Hierarchy<TP>& H, PcgWork<T, TP
           const bool first = virtual_r0 && !r0_consumed;  // (r holds nothing yet: the kernel synthesises r0)
           rr_fused_rows = lattice_rupd_restrict<T, K>(*dia, L0.Ql, (const CgScalars*)S, (const T*)pcur, (const T*)r, rnew,
                                                       dptr<T>(H.levels[1].b), pb, st, nullptr, nullptr, nullptr,
-                                                      first ? pp.pair_src : nullptr, pp.pair_dst, pp.pair_cols);
+                                                      first ? pp.pair_src : nullptr, need_x ? nullptr : pp.pair_dst,
+                                                      pp.pair_cols, x);
           r0_consumed = true;
           rsel ^= 1;
           r = rnew;
@@ -1095,6 +1121,7 @@ inline PcgBatchResult pcg_solve(const Csr<T>& A, Hierarchy<TP>& H, PcgWork<T, TP
       const int todo = (int)std::min<int64_t>(chunk, (int64_t)pp.itmax - it);
       gkey.criterion = criterion;
       gkey.parity = parity | (rsel << 1);
+      gkey.fused = fused_rr ? 1 : 0;
       hipGraphExec_t ge = (want_graph && it > 0 && todo == chunk) ? chunk_graph() : nullptr;
       if (ge) {
         CS_HIP(hipGraphLaunch(ge, st));
@@ -1231,6 +1258,8 @@ inline PcgBatchResult pcg_solve(const Csr<T>& A, Hierarchy<TP>& H, PcgWork<T, TP
     res.resid_bytes = n * 5 * (int64_t)sizeof(T) + n * K * ((int64_t)sizeof(TP) + 2 * (int64_t)sizeof(T) + (MIXED ? (int64_t)sizeof(TP) : 0));
     if (res.resid_fused && H.levels.size() > 1)
       res.resid_bytes += n * 9 * (int64_t)sizeof(T) + (int64_t)H.levels[1].A.nrows * K * (int64_t)sizeof(T);
+    // (the fused pass that carries the solution: x read and written; the two-pass figure has never counted x)
+    if (res.resid_fused && need_x) res.resid_bytes += 2 * n * K * (int64_t)sizeof(T);
     if (!recompute) res.resid_bytes = 0;  // (the generic update kernel: not this formula)
   }
   res.graph_launches = graph_launches;

@@ -234,12 +234,20 @@ typedef struct csgpu_opts {
                                  2-hop balls predicts nnz(P) / nnz(A); above 0.8 the graph is an expander whose aggregation the
                                  set-up would throw away (nnz(P) > 0.75 nnz(A)) and the handle gets its one level at once
                                  (BASELINE configs[4]: 0.20 -> 0.03 s of device set-up); -1 = always aggregate first */
-  int32_t fused_restrict;     /* lattice path, batches of 16 / 32 columns in one precision, resistance-only pair solves: 1 = the
-                                 residual update and the restriction of the V-cycle run as ONE marching pass over r (the
+  int32_t fused_restrict;     /* lattice path, batches of 16 / 32 columns in one precision: 1 = the residual update and the
+                                 restriction of the V-cycle run as ONE marching pass over r WHEREVER that pass exists (the
                                  residual ping-pongs between two buffers: + n x batch values of device memory; results are
-                                 those of the two-pass path bit for bit); -1 = two passes; 0 = fused in double precision
-                                 (+7 % pair-solves/s at 10000^2), two passes in single precision (where the fused pass is
-                                 3 - 5 % slower). Levels with enriched aggregates (rasters with
+                                 those of the two-pass path bit for bit) -- resistance-only pair solves and, with this value
+                                 only, the solves that carry the whole solution (csgpu_solve_pairs with volt_out,
+                                 csgpu_solve_pairs_currents, csgpu_solve_rhs, csgpu_solve_grounded / _sources without
+                                 Dirichlet sets, their csgpu_multi_ twins): the pass then also runs x += alpha p on the
+                                 cells it owns, and the second residual buffer comes on top of x, b and A p (when there is
+                                 no memory for it the solve runs two passes); -1 = two passes everywhere; 0 = fused for
+                                 resistance-only pair solves in double precision (+7 % pair-solves/s at 10000^2), two passes
+                                 in single precision (where the fused pass is 3 - 5 % slower) and
+                                 for every solve that carries the solution (A/B: DESIGN.md section 4a,
+                                 tools/ab_fused_solution.py). Not with an fp32 hierarchy under the fp64 iteration, Dirichlet
+                                 sets or polygon handles. Levels with enriched aggregates (rasters with
                                  NODATA cells, csrc/enrich.h) take the fused pass too: the enrichment's change of the residual
                                  reaches b_c through a coarse-side correction (W = Q'AE), whose sums run in another order --
                                  THERE the fused and the two-pass results agree to rounding, not bit for bit */
@@ -348,7 +356,9 @@ typedef struct csgpu_stats {
   int64_t resid_calls;          /* number of those launches */
   int64_t resid_bytes;          /* algorithmic bytes of ONE of them: n*5*val + n*K*(p + 2 r [+ the copy of r in the
                                    preconditioner's precision]); fused with the restriction (resid_fused): + n*9*val +
-                                   n_coarse*K*val. 0 when the update is not the lattice kernel */
+                                   n_coarse*K*val, and + 2*n*K*val when that pass also updates the solution (the two-pass
+                                   figure does NOT count x, which its update reads and writes as well when the solution is
+                                   carried). 0 when the update is not the lattice kernel */
   int32_t resid_fused;          /* 1 = those launches are the fused residual update + restriction (csgpu_opts.fused_restrict) */
   int32_t reserved_stats;
 } csgpu_stats;
