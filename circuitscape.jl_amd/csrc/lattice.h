@@ -259,20 +259,9 @@ inline int lattice_segc() {  // coarse columns per restriction tile (tuning knob
 // columns and the residual slot one. 512 threads: TIC = 32 coarse rows at K = 32 (halo 8 of 104 staged rows), 130 KB of LDS.
 // The arithmetic of an entry is that of dia_cg_kernel<..., DIA_RUPD> (same products, same order): r_out is bit-identical to
 // the unfused update's; the coarse sums are lattice_restrict_kernel's, bit for bit. Only the order in which the partials of
-// r'r are summed differs.
+// r'r are summed differs. RupdRestrictOpts: what a launch may carry besides r, p and the coarse sums.
 template <class T>
-struct RupdRestrictArgs {
-  int64_t n;
-  int R, C, Rc, Cc;
-  int nstrips, nseg, segc;
-  const T* rows;        // lattice form of A, [n][5]
-  const T* q;           // index-free Q, [n][9]
-  const T* p;           // search direction, [n][K]
-  const T* r_in;        // [n][K]
-  T* r_out;             // [n][K], must not alias r_in
-  T* bc;                // [Rc*Cc][K]
-  const CgScalars* S;   // alpha[c], all_done
-  double* partials;     // [gridDim.x][K] partials of r_out'r_out (may be null)
+struct RupdRestrictOpts {
   // streaming pair solves (pcg_stream_pairs): a column with restart[c] != 0 takes a new pair -- its new residual is the
   // pair's right-hand side, -1 at node src[c] and +1 at dst[c] (nothing when they coincide), which stream_restart_kernel
   // writes AFTER the two-pass update; here the coarse sums need it at once
@@ -284,12 +273,27 @@ struct RupdRestrictArgs {
   const int* isrc = nullptr;
   const int* idst = nullptr;
   int icols = 0;
-  // APPLY form of the kernel (a lattice V(2,2) level, pcg.h): r_out = D p and bc = Q^T p in one pass over p -- `rows` is the
-  // lattice form of D (the level's two-sweep operator S), r_in / S / partials are unused, `skip` is the cycle's skip flag
-  const int* skip = nullptr;
   // XUP form (a solve that carries the whole solution, pcg.h): xsol += alpha p at the OWNED entries, the arithmetic of the
   // two-pass update (stencil.h). Never with APPLY, restart / src / dst or isrc / idst (such solves store b).
   T* xsol = nullptr;
+};
+
+template <class T>
+struct RupdRestrictArgs : RupdRestrictOpts<T> {
+  int64_t n;
+  int R, C, Rc, Cc;
+  int nstrips, nseg, segc;
+  const T* rows;        // lattice form of A, [n][5]
+  const T* q;           // index-free Q, [n][9]
+  const T* p;           // search direction, [n][K]
+  const T* r_in = nullptr;  // [n][K]
+  T* r_out;             // [n][K], must not alias r_in
+  T* bc;                // [Rc*Cc][K]
+  const CgScalars* S = nullptr;  // alpha[c], all_done
+  double* partials = nullptr;    // [gridDim.x][K] partials of r_out'r_out (may be null)
+  // APPLY form of the kernel (a lattice V(2,2) level, pcg.h): r_out = D p and bc = Q^T p in one pass over p -- `rows` is the
+  // lattice form of D (the level's two-sweep operator S), r_in / S / partials are unused, `skip` is the cycle's skip flag
+  const int* skip = nullptr;
 };
 
 template <class T, int K, int NT>
@@ -663,47 +667,43 @@ inline int lattice_rupd_restrict_grid(const LatticeQ<T>& Q, int& nstrips, int& n
   return (int)std::max<int64_t>(g, 1);
 }
 
+// geometry and operators of one launch of lattice_rupd_restrict_kernel (every form); returns the grid
+template <class T, int K>
+inline int lattice_rupd_args(const Dia<T>& D, const LatticeQ<T>& Q, const T* p, T* r_out, T* bc, RupdRestrictArgs<T>& a) {
+  a.n = D.n;
+  a.R = Q.R;
+  a.C = Q.C;
+  a.Rc = Q.Rc;
+  a.Cc = Q.Cc;
+  a.rows = D.data();
+  a.q = Q.data();
+  a.p = p;
+  a.r_out = r_out;
+  a.bc = bc;
+  return lattice_rupd_restrict_grid<T, K>(Q, a.nstrips, a.nseg, a.segc);
+}
+
 // r_out = r_in - alpha (A p) and bc = Q^T r_out in one pass; returns the number of partial rows written (0: none asked for)
 template <class T, int K>
 inline int lattice_rupd_restrict(const Dia<T>& D, const LatticeQ<T>& Q, const CgScalars* S, const T* p, const T* r_in, T* r_out,
-                                 T* bc, double* partials, hipStream_t st, const int* restart = nullptr,
-                                 const int* src = nullptr, const int* dst = nullptr, const int* isrc = nullptr,
-                                 const int* idst = nullptr, int icols = 0, T* xsol = nullptr) {
+                                 T* bc, double* partials, hipStream_t st, const RupdRestrictOpts<T>& o = RupdRestrictOpts<T>()) {
   // (a solve that carries the solution stores b: no streaming restart, no synthesised first residual)
-  CS_REQUIRE(!xsol || (!restart && !src && !dst && !isrc && !idst), CSGPU_INTERNAL,
+  CS_REQUIRE(!o.xsol || (!o.restart && !o.src && !o.dst && !o.isrc && !o.idst), CSGPU_INTERNAL,
              "fused residual update: the solution update takes a stored residual");
-  if constexpr (lattice_rupd_restrict_fits<T, K>()) {
-    constexpr int NT = kFusedNT;
+  if constexpr (!lattice_rupd_restrict_fits<T, K>()) {
+    return 0;
+  } else {
     RupdRestrictArgs<T> a;
-    a.n = D.n;
-    a.R = Q.R;
-    a.C = Q.C;
-    a.Rc = Q.Rc;
-    a.Cc = Q.Cc;
-    const int g = lattice_rupd_restrict_grid<T, K>(Q, a.nstrips, a.nseg, a.segc);
-    a.rows = D.data();
-    a.q = Q.data();
-    a.p = p;
+    const int g = lattice_rupd_args<T, K>(D, Q, p, r_out, bc, a);
     a.r_in = r_in;
-    a.r_out = r_out;
-    a.bc = bc;
     a.S = S;
     a.partials = partials;
-    a.restart = restart;
-    a.src = src;
-    a.dst = dst;
-    a.isrc = isrc;
-    a.idst = idst;
-    a.icols = icols;
-    a.xsol = xsol;
-    if (xsol)
-      hipLaunchKernelGGL((lattice_rupd_restrict_kernel<T, K, NT, false, true>), dim3(g), dim3(NT), 0, st, a);
+    static_cast<RupdRestrictOpts<T>&>(a) = o;
+    if (o.xsol)
+      hipLaunchKernelGGL((lattice_rupd_restrict_kernel<T, K, kFusedNT, false, true>), dim3(g), dim3(kFusedNT), 0, st, a);
     else
-      hipLaunchKernelGGL((lattice_rupd_restrict_kernel<T, K, NT>), dim3(g), dim3(NT), 0, st, a);
+      hipLaunchKernelGGL((lattice_rupd_restrict_kernel<T, K, kFusedNT>), dim3(g), dim3(kFusedNT), 0, st, a);
     return partials ? g : 0;
-  } else {
-    (void)D; (void)Q; (void)S; (void)p; (void)r_in; (void)r_out; (void)bc; (void)partials; (void)st; (void)restart; (void)src; (void)dst; (void)isrc; (void)idst; (void)icols; (void)xsol;
-    return 0;
   }
 }
 
@@ -712,29 +712,14 @@ inline int lattice_rupd_restrict(const Dia<T>& D, const LatticeQ<T>& Q, const Cg
 template <class T, int K>
 inline bool lattice_apply_restrict(const Dia<T>& D, const LatticeQ<T>& Q, const T* x, T* y, T* bc, const int* skip,
                                    hipStream_t st) {
-  if constexpr (lattice_rupd_restrict_fits<T, K>()) {
-    constexpr int NT = kFusedNT;
-    RupdRestrictArgs<T> a;
-    a.n = D.n;
-    a.R = Q.R;
-    a.C = Q.C;
-    a.Rc = Q.Rc;
-    a.Cc = Q.Cc;
-    const int g = lattice_rupd_restrict_grid<T, K>(Q, a.nstrips, a.nseg, a.segc);
-    a.rows = D.data();
-    a.q = Q.data();
-    a.p = x;
-    a.r_in = nullptr;
-    a.r_out = y;
-    a.bc = bc;
-    a.S = nullptr;
-    a.partials = nullptr;
-    a.skip = skip;
-    hipLaunchKernelGGL((lattice_rupd_restrict_kernel<T, K, NT, true>), dim3(g), dim3(NT), 0, st, a);
-    return true;
-  } else {
-    (void)D; (void)Q; (void)x; (void)y; (void)bc; (void)skip; (void)st;
+  if constexpr (!lattice_rupd_restrict_fits<T, K>()) {
     return false;
+  } else {
+    RupdRestrictArgs<T> a;
+    const int g = lattice_rupd_args<T, K>(D, Q, x, y, bc, a);
+    a.skip = skip;
+    hipLaunchKernelGGL((lattice_rupd_restrict_kernel<T, K, kFusedNT, true>), dim3(g), dim3(kFusedNT), 0, st, a);
+    return true;
   }
 }
 

@@ -8,6 +8,7 @@
 // pre-smoothing sweep from the zero guess needs no matrix product at all.
 #pragma once
 #include <algorithm>
+#include <deque>
 #include <limits>
 #include <type_traits>
 
@@ -73,6 +74,12 @@ inline bool fused_restrict_wanted() {
 #ifndef CSGPU_CHAIN_L1_FP64
 #define CSGPU_CHAIN_L1_FP64 1
 #endif
+// Knobs::fused_level1 resolved for the front half (x = S b and b_c = Q2' b in one pass): 0 = on in double precision
+template <class T>
+inline bool fused_level1_wanted() {
+  const int f = knobs().fused_level1;
+  return f > 0 || (f == 0 && sizeof(T) == 8);
+}
 template <class T>
 inline bool chained_level1_default() {
   return sizeof(T) == 8 && CSGPU_CHAIN_L1_FP64 != 0;
@@ -97,31 +104,24 @@ struct VcycleFuse {
 // Levels from `first` down run in one launch (tail.h) when they are small: the first level l >= 1 with at most
 // 4096 rows (measured: above that one workgroup per column is slower than the launches it replaces), provided at least two
 // levels are left. CSGPU_TAIL_ROWS=0 switches the tail off (A/B knob).
-template <class T>
-inline int tail_first_level(Hierarchy<T>& H) {
-  if (H.tail_first != -2) return H.tail_first;
-  const int rows = knobs().tail_rows;  // (read once per hierarchy)
-  H.tail_first = -1;
-  const int nl = (int)H.levels.size();
-  for (int l = 1; l + 1 < nl; ++l) {
-    if (H.levels[l].A.nrows <= rows && nl - l <= kTailMaxLevels) {
-      H.tail_first = l;
-      if (knobs().tail_debug) fprintf(stderr, "csgpu: coarse tail from level %d (%d rows) of %d\n", l, H.levels[l].A.nrows, nl);
-      break;
-    }
-  }
-  return H.tail_first;
-}
-
 // what tail_first_level would decide, without deciding it (csgpu_get_info on a handle that has not solved yet)
 template <class T>
 inline int tail_first_level_peek(const Hierarchy<T>& H) {
   if (H.tail_first != -2) return H.tail_first;
-  const int rows = knobs().tail_rows;
+  const int rows = knobs().tail_rows;  // (read once per hierarchy)
   const int nl = (int)H.levels.size();
   for (int l = 1; l + 1 < nl; ++l)
     if (H.levels[l].A.nrows <= rows && nl - l <= kTailMaxLevels) return l;
   return -1;
+}
+
+template <class T>
+inline int tail_first_level(Hierarchy<T>& H) {
+  if (H.tail_first != -2) return H.tail_first;
+  const int l = H.tail_first = tail_first_level_peek(H);
+  if (l >= 1 && knobs().tail_debug)
+    fprintf(stderr, "csgpu: coarse tail from level %d (%d rows) of %d\n", l, H.levels[l].A.nrows, (int)H.levels.size());
+  return l;
 }
 
 template <class T, int K>
@@ -211,6 +211,10 @@ inline void vcycle(Hierarchy<T>& H, int l, const T* b, T* out, int nu_pre0, int 
   auto weight = [&](int sweep) { return cheb ? (T)L.weights[sweep] : (T)L.omega; };
   const bool want_dot = fuse && fuse->dotw && l == 0;
   const int* skip = fuse ? fuse->skip : nullptr;
+  auto dot_with_out = [&]() {  // partials of dotw . out by a launch of its own: a last product that cannot carry them
+    hipLaunchKernelGGL((dot_kernel<T, K, false>), dim3(spmv_grid<T, K>(n)), dim3(256), 0, st, (int64_t)n, fuse->dotw,
+                       (const T*)out, fuse->partials, (const T*)nullptr, (const T*)nullptr, (double*)nullptr);
+  };
   if (l >= 1 && l == tail_first_level(H)) {
     const int nu1 = nu_l1 > 0 ? nu_l1 : nu_coarse, nud = nu_deep > 0 ? nu_deep : nu_coarse + 1;
     launch_tail<T, K>(H, l, b, out, nu1, nud, skip, st);
@@ -223,9 +227,7 @@ inline void vcycle(Hierarchy<T>& H, int l, const T* b, T* out, int nu_pre0, int 
     if (dirichlet)
       hipLaunchKernelGGL((dense_dirichlet_kernel<T, K>), dim3(K), dim3(256), 0, st, n, (const T*)dptr<T>(H.coarse_cand),
                          (const int*)dptr<int>(H.coarse_comp), H.dir_ncomp, H.dir_coef, H.dir_mode, b, out, skip);
-    if (want_dot)
-      hipLaunchKernelGGL((dot_kernel<T, K, false>), dim3(spmv_grid<T, K>(n)), dim3(256), 0, st, (int64_t)n, fuse->dotw,
-                         (const T*)out, fuse->partials, (const T*)nullptr, (const T*)nullptr, (double*)nullptr);
+    if (want_dot) dot_with_out();
     return;
   }
   if (!(l == 0 && fuse && fuse->b_has_tail && nu_pre == 1 && nu_post == 1 && L.two_product()) &&
@@ -238,9 +240,10 @@ inline void vcycle(Hierarchy<T>& H, int l, const T* b, T* out, int nu_pre0, int 
   T* oth = dptr<T>(L.rb);
   const T omega = (T)L.omega;
   const bool use25 = K >= 8 && L.A25.n == n && n > 0;  // refined-tile lattice level: index-free products with A (dia25.h)
+  constexpr int K25 = K >= 8 ? K : 8;                  // (the 25-point kernels exist from that batch width up)
   auto jacobi_sweep = [&](const T* xin, T* xout, bool dot, int sweep = 0) {
     if (use25 && !dot) {
-      dia25_launch<T, (K >= 8 ? K : 8)>(L.A25, D25_JACOBI, xin, xout, b, (const T*)dptr<T>(L.dinv), weight(sweep), skip, st);
+      dia25_launch<T, K25>(L.A25, D25_JACOBI, xin, xout, b, (const T*)dptr<T>(L.dinv), weight(sweep), skip, st);
       return;
     }
     SpmvArgs<T> a = level_args(L, xin, xout, skip);
@@ -262,9 +265,7 @@ inline void vcycle(Hierarchy<T>& H, int l, const T* b, T* out, int nu_pre0, int 
     const int sweeps = want == 0 ? (H.levels.size() == 1 ? kSingleLevelSweeps : 8) : std::max(want, 0);
     if (sweeps <= 0) {
       hipLaunchKernelGGL((scale_dinv_kernel<T, K>), dim3(gv), dim3(256), 0, st, (int64_t)n, out, b, dptr<T>(L.dinv), omega, skip);
-      if (want_dot)
-        hipLaunchKernelGGL((dot_kernel<T, K, false>), dim3(spmv_grid<T, K>(n)), dim3(256), 0, st, (int64_t)n, fuse->dotw,
-                           (const T*)out, fuse->partials, (const T*)nullptr, (const T*)nullptr, (double*)nullptr);
+      if (want_dot) dot_with_out();
       return;
     }
     for (int s = 0; s < sweeps; ++s) {
@@ -274,11 +275,18 @@ inline void vcycle(Hierarchy<T>& H, int l, const T* b, T* out, int nu_pre0, int 
     }
     return;
   }
+  // the next level: its right-hand side, its solution behind it, its cycle
+  Level<T>& Lc = H.levels[l + 1];
+  T* bc = dptr<T>(Lc.b);
+  T* xc = bc + (size_t)std::max(Lc.A.nrows, 1) * K;
+  auto coarse_cycle = [&](const T* bcoarse, T* xcoarse) {
+    VcycleFuse<T> cf;
+    cf.skip = skip;
+    vcycle<T, K>(H, l + 1, bcoarse, xcoarse, nu_pre0, nu_post0, nu_coarse, st, &cf);
+  };
   if (l == 0 && fuse && fuse->b_has_tail && nu_pre == 1 && nu_post == 1 && L.two_product()) {
     // two-product form of the level (build_sq_kernel): b_c = Q^T b ; x_c = coarse(b_c) ; out = [S Q][b; x_c]
-    Level<T>& Lc = H.levels[l + 1];
-    T* bc = dptr<T>(Lc.b);
-    T* xc = const_cast<T*>(b) + (size_t)n * K;
+    xc = const_cast<T*>(b) + (size_t)n * K;
     if (L.lattice_two_product()) {
       if (!fuse->bc_ready) lattice_restrict<T, K>(L.Ql, b, bc, skip, st);  // index-free Q^T b (lattice.h)
     } else {
@@ -287,9 +295,7 @@ inline void vcycle(Hierarchy<T>& H, int l, const T* b, T* out, int nu_pre0, int 
       a.order_lr = L.orderQT.p ? dptr<int>(L.orderQT) : nullptr;
       spmv_launch<T, K>(a, EPI_PLAIN, false, st);
     }
-    VcycleFuse<T> cf;
-    cf.skip = skip;
-    vcycle<T, K>(H, l + 1, bc, xc, nu_pre0, nu_post0, nu_coarse, st, &cf);
+    coarse_cycle(bc, xc);
     if (want_dot) CS_REQUIRE(fuse->dotw == b, CSGPU_INTERNAL, "two-product level: fused dot must be with the input vector");
     if (L.lattice_two_product()) {
       // S in lattice form + index-free Q, one marching kernel (stencil.h); partials of b'out always written
@@ -309,19 +315,13 @@ inline void vcycle(Hierarchy<T>& H, int l, const T* b, T* out, int nu_pre0, int 
   }
   if (l >= 1 && L.lattice_v22() && nu_pre == 2 && nu_post == 2) {
     // lattice form of the level (lattice_level1_setup, lattice_setup.h): four marching products, no column index
-    Level<T>& Lc = H.levels[l + 1];
-    const size_t celems = (size_t)std::max(Lc.A.nrows, 1) * K;
-    T* bc = dptr<T>(Lc.b);
-    T* xc = dptr<T>(Lc.b) + celems;
     // x = S b (the two pre-sweeps) and b_c = Q2' b (residual + restriction): one pass over b, or two
     const int f1 = knobs().fused_level1;
-    if (!((f1 > 0 || (f1 == 0 && sizeof(T) == 8)) && lattice_apply_restrict<T, K>(L.Sdia, L.Ql, b, cur, bc, skip, st))) {
+    if (!(fused_level1_wanted<T>() && lattice_apply_restrict<T, K>(L.Sdia, L.Ql, b, cur, bc, skip, st))) {
       dia_apply<T, K>(L.Sdia, b, cur, (const T*)nullptr, skip, st);
       lattice_restrict<T, K>(L.Ql, b, bc, skip, st);
     }
-    VcycleFuse<T> cf;
-    cf.skip = skip;
-    vcycle<T, K>(H, l + 1, bc, xc, nu_pre0, nu_post0, nu_coarse, st, &cf);
+    coarse_cycle(bc, xc);
     // out = x + S (b - A x) + Q2 x_c (residual, prolongation + post-sweeps): one chained pass that keeps t = b - A x on chip
     // (stencil.h; fused_level1 = 2), or two launches with t stored
     if ((f1 >= 2 || (f1 == 0 && chained_level1_default<T>())) &&
@@ -339,8 +339,7 @@ inline void vcycle(Hierarchy<T>& H, int l, const T* b, T* out, int nu_pre0, int 
     const bool no_j0 = !knobs().dia25_fused_j0;  // A/B knob
     if (use25 && nu_pre >= 2 && !no_j0 && !(fuse && fuse->xa_ready && l == 0)) {
       // 25-point lattice level: the sweep from zero and the first real sweep in one marching pass (dia25.h, JACOBI0)
-      dia25_launch<T, (K >= 8 ? K : 8)>(L.A25, D25_JACOBI0, (const T*)nullptr, oth, b, (const T*)dptr<T>(L.dinv), weight(1), skip, st,
-                                        omega);
+      dia25_launch<T, K25>(L.A25, D25_JACOBI0, (const T*)nullptr, oth, b, (const T*)dptr<T>(L.dinv), weight(1), skip, st, omega);
       std::swap(cur, oth);
       s_first = 2;
     } else if (!(fuse && fuse->xa_ready && l == 0)) {
@@ -355,25 +354,19 @@ inline void vcycle(Hierarchy<T>& H, int l, const T* b, T* out, int nu_pre0, int 
   }
   // residual r = b - A x  -> oth
   if (use25) {
-    dia25_launch<T, (K >= 8 ? K : 8)>(L.A25, D25_RESID, (const T*)cur, oth, b, (const T*)nullptr, T(0), skip, st);
+    dia25_launch<T, K25>(L.A25, D25_RESID, (const T*)cur, oth, b, (const T*)nullptr, T(0), skip, st);
   } else {
     SpmvArgs<T> a = level_args(L, (const T*)cur, oth, skip);
     a.b = b;
     spmv_launch<T, K>(a, EPI_RESID, false, st);
   }
   // restrict: b_{l+1} = R r
-  Level<T>& Lc = H.levels[l + 1];
-  const size_t celems = (size_t)std::max(Lc.A.nrows, 1) * K;
-  T* bc = dptr<T>(Lc.b);
-  T* xc = dptr<T>(Lc.b) + celems;
   {
     SpmvArgs<T> a = spmv_args(L.R, (const T*)oth, bc);
     a.skip = skip;
     spmv_launch<T, K>(a, EPI_PLAIN, false, st);
   }
-  VcycleFuse<T> cf;
-  cf.skip = skip;
-  vcycle<T, K>(H, l + 1, bc, xc, nu_pre0, nu_post0, nu_coarse, st, &cf);
+  coarse_cycle(bc, xc);
   if (nu_post >= 1 && L.Q.nnz > 0) {
     // fused prolongation + first post-smoothing sweep: x' = x + omega D^-1 r + Q xc   (r = b - A x is still in `oth`)
     const bool fin = (nu_post == 1);
@@ -424,9 +417,7 @@ inline void vcycle(Hierarchy<T>& H, int l, const T* b, T* out, int nu_pre0, int 
     }
   } else {
     CS_HIP(hipMemcpyAsync(out, cur, (size_t)n * K * sizeof(T), hipMemcpyDeviceToDevice, st));
-    if (want_dot)
-      hipLaunchKernelGGL((dot_kernel<T, K, false>), dim3(spmv_grid<T, K>(n)), dim3(256), 0, st, (int64_t)n, fuse->dotw,
-                         (const T*)out, fuse->partials, (const T*)nullptr, (const T*)nullptr, (double*)nullptr);
+    if (want_dot) dot_with_out();
   }
 }
 
@@ -499,6 +490,34 @@ struct PcgGraphKey {
 
 static const int kEnrichRows = 256;  // = kEnrichParts of enrich.h: extra rows of part_a
 
+struct Event {  // (owned: nothing leaks when a CS_REQUIRE or CS_HIP throws)
+  hipEvent_t e = nullptr;
+  Event() { CS_HIP(hipEventCreate(&e)); }
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() { hipEventDestroy(e); }
+};
+
+// Event pairs around launches: grows on demand. PcgWork keeps one per kind of timed launch; a solve's own (one pair around
+// all of it) lives and dies with the call.
+struct LaunchTimer {
+  std::deque<Event> ev;
+  void begin(int slot, hipStream_t st) {
+    while ((int)ev.size() < 2 * (slot + 1)) ev.emplace_back();
+    CS_HIP(hipEventRecord(ev[2 * slot].e, st));
+  }
+  void end(int slot, hipStream_t st) { CS_HIP(hipEventRecord(ev[2 * slot + 1].e, st)); }
+  double sum_ms(int counted) const {  // of the first `counted` pairs
+    double ms = 0;
+    for (int t = 0; t < counted; ++t) {
+      float m = 0;
+      CS_HIP(hipEventElapsedTime(&m, ev[2 * t].e, ev[2 * t + 1].e));
+      ms += m;
+    }
+    return ms;
+  }
+};
+
 // T = precision of the CG iteration (matrix seen by CG, x, r, p, Ap); TP = precision of the AMG hierarchy and of
 // everything inside the V-cycle (TP == T, or TP = float under T = double: "fp32 preconditioner").
 template <class T, class TP>
@@ -523,8 +542,8 @@ struct PcgWork {
   DBuf part_a, part_b, part_c;
   DBuf part_ca, part_cc;      // collapsed copies of part_a / part_c (collapse_partials_kernel)
   DBuf part_cb;               // collapsed copy of part_b (streaming solves: ||r||^2 of every iteration)
-  std::vector<hipEvent_t> ev;  // event pairs around the CG SpMV launches
-  std::vector<hipEvent_t> ev2; // ... and around the residual-update launches of the same iterations
+  LaunchTimer ev;   // around the CG SpMV launches
+  LaunchTimer ev2;  // ... and around the residual-update launches of the same iterations
   std::vector<std::pair<PcgGraphKey, hipGraphExec_t>> graphs;  // captured iteration chunks
   bool graph_broken = false;                                   // capture failed once: stay on direct launches
   void drop_graphs() {
@@ -568,9 +587,9 @@ struct PcgWork {
     part_ca.alloc((size_t)kCollapsedParts * kMaxK * sizeof(double));
     part_cc.alloc((size_t)kCollapsedParts * kMaxK * sizeof(double));
   }
-  // b / Ap on demand (see ensure)
-  T* need_vec(DBuf& v) {
-    const size_t bytes = (size_t)n * K * sizeof(T);
+  // b / Ap / x on demand (see ensure); p2 with the element size of TP
+  T* need_vec(DBuf& v, size_t elem = sizeof(T)) {
+    const size_t bytes = (size_t)n * K * elem;
     if (v.bytes < bytes) {
       drop_graphs();
       v.alloc(bytes);
@@ -592,11 +611,7 @@ struct PcgWork {
       CS_HIP(hipStreamSynchronize(st));
     }
   }
-  ~PcgWork() {
-    drop_graphs();
-    for (auto e : ev) hipEventDestroy(e);
-    for (auto e : ev2) hipEventDestroy(e);
-  }
+  ~PcgWork() { drop_graphs(); }
 };
 
 struct PcgBatchResult {
@@ -630,455 +645,522 @@ inline bool column_accepted(double relres, int done, bool explicit_relres) {
   return true;
 }
 
-// Solve A X = B for the K interleaved columns held in W.b. With pp.need_x the solution is left in W.x; otherwise only
-// the entries at W.fnode are accumulated (W.xf) and W.x is not touched (not even allocated).
-// A is the matrix CG sees (precision T); H is the hierarchy (precision TP) whose level 0 has A's sparsity pattern.
-// `dia`: optional symmetric-diagonal (lattice) form of A (stencil.h); when given, the product A p is evaluated from it
-// with the search-direction update p = z + beta p fused in, and A's CSR form is only used by the explicit post-check.
+// ---- pieces the batch loop (pcg_solve) and the streaming loop (pcg_stream_pairs) share ---------------------------------
+
+// The resolved pointers of a PcgWork.
+template <class T, class TP>
+struct PcgPtrs {
+  T* r = nullptr;                    // W.r: buffer 0 of the residual ping-pong
+  TP* pbuf[2] = {nullptr, nullptr};  // search direction (stencil path: ping-pong; CSR path: one buffer twice)
+  TP *z = nullptr, *rp = nullptr;    // rp: the residual in the V-cycle's precision (aliases r when TP == T)
+  CgScalars* S = nullptr;
+  double *pa = nullptr, *pb = nullptr, *pc = nullptr;  // partial rows: r'z, r'r, p'Ap
+  // partial rows of the big SpMM-shaped launches are collapsed before the single-workgroup scalar kernels read them
+  double *pac = nullptr, *pcc = nullptr;
+  double atol = 0;
+  int collapse_min = 0;  // (Knobs::collapse_min: test knob, so that a test can exercise the path on a small problem)
+};
+
+template <class T, class TP>
+inline PcgPtrs<T, TP> pcg_ptrs(PcgWork<T, TP>& W, const PcgParams& pp, bool second_p) {
+  if (second_p) W.need_vec(W.p2, sizeof(TP));
+  PcgPtrs<T, TP> w;
+  w.r = dptr<T>(W.r);
+  w.pbuf[0] = dptr<TP>(W.p);
+  w.pbuf[1] = second_p ? dptr<TP>(W.p2) : dptr<TP>(W.p);
+  w.z = dptr<TP>(W.z);
+  w.rp = std::is_same<T, TP>::value ? (TP*)w.r : dptr<TP>(W.rp);
+  w.S = dptr<CgScalars>(W.scalars);
+  w.pa = dptr<double>(W.part_a);
+  w.pb = dptr<double>(W.part_b);
+  w.pc = dptr<double>(W.part_c);
+  w.pac = dptr<double>(W.part_ca);
+  w.pcc = dptr<double>(W.part_cc);
+  w.atol = pp.atol < 0 ? std::sqrt((double)std::numeric_limits<T>::epsilon()) : pp.atol;
+  w.collapse_min = knobs().collapse_min >= 0 ? (int)std::max<int64_t>(1, knobs().collapse_min) : 4 * kCollapsedParts;
+  return w;
+}
+
+// the rows a scalar kernel reads: `src` itself, or its collapsed copy in `dst`
+template <int K>
+inline std::pair<const double*, int> collapse_partials(double* src, int nparts, double* dst, int collapse_min, hipStream_t st) {
+  if (nparts <= collapse_min) return {src, nparts};
+  hipLaunchKernelGGL((collapse_partials_kernel<K>), dim3(ceil_div(kCollapsedParts * K, 256)), dim3(256), 0, st,
+                     (const double*)src, nparts, dst);
+  return {dst, kCollapsedParts};
+}
+
+// Fused residual update + restriction (lattice.h, Knobs::fused_restrict): r_new = r - alpha A p and b_c = Q^T r_new in one
+// pass. The residual then ping-pongs between W.r and W.r2: the loops flip() after every fused launch, and which buffer holds
+// the current residual is part of the graph key. A two-pass solve stays in buffer 0.
+template <class T, class TP>
+struct ResidualPingPong {
+  T* rbuf[2] = {nullptr, nullptr};
+  TP* copy = nullptr;  // TP != T: the residual's copy in the preconditioner's precision (one buffer: such solves never flip)
+  int sel = 0;
+  T* cur() const { return rbuf[sel]; }
+  TP* cur_p() const {  // the V-cycle's input, and the vector its fused dot is taken with (apply_preconditioner)
+    if constexpr (std::is_same<T, TP>::value) return rbuf[sel]; else return copy;
+  }
+  T* next() const { return rbuf[sel ^ 1]; }
+  void flip() { sel ^= 1; }
+  void select(int i) { sel = i; }
+  int snapshot() const { return sel; }  // capturing a chunk executes nothing: the flips it made on the host are undone
+  void restore(int s) { sel = s; }
+  // Launches enqueued after the last column stopped returned without writing (device flag), yet each flipped on the host:
+  // the residual is in the buffer the last REAL update wrote -- update number `real` = max_c iters[c] of this solve (buffer 0
+  // holds r_0).
+  void rewind_to_update(int real) { select(real & 1); }
+};
+
+// Which solves take the fused pass. One precision only (the V-cycle reads r itself), solves without masks or projections
+// (which touch r between the update and the cycle). An ENRICHED level takes it when the set-up built W = Q'AE
+// (EN.ntouch > 0): enrich_pre changes r on its halo cells after the pass has restricted it, and enrich_coarse_fix applies
+// the restriction's share of that change to b_c (enrich.h). A solve that carries the whole solution takes it only when asked
+// to (Knobs::fused_restrict = 1): the pass then also runs x += alpha p on the cells it owns (the XUP form of the kernel), and
+// W.r2 comes ON TOP of x, b and A p -- the default leaves such a solve's device memory as it was.
+// Returns the rows of r'r partials a launch of the pass writes (one per workgroup) once the second residual buffer (with the
+// tail) exists, 0 = the solve runs two passes. `release_unused`: give a buffer an earlier solve left back first (a solve that
+// carries x, b and A p).
 template <class T, class TP, int K>
-inline PcgBatchResult pcg_solve(const Csr<T>& A, Hierarchy<TP>& H, PcgWork<T, TP>& W, const PcgParams& pp,
-                                int ncols_active, hipStream_t st, const Dia<T>* dia = nullptr) {
-  constexpr bool MIXED = !std::is_same<T, TP>::value;
+inline int acquire_fused_residual(Hierarchy<TP>& H, PcgWork<T, TP>& W, const PcgParams& pp, int64_t n, bool enrich, bool recompute,
+                                  bool lattice_two_product, bool need_x, bool masked, bool release_unused) {
+  int rows = 0;
+  if constexpr (std::is_same<T, TP>::value && lattice_rupd_restrict_fits<T, K>()) {
+    bool fused = fused_restrict_wanted<T>() && recompute && lattice_two_product && (!need_x || knobs().fused_restrict > 0) &&
+                 !masked && (!enrich || H.enr.ntouch > 0) && pp.nu_pre == 1 && pp.nu_post == 1;
+    const size_t want = ((size_t)n + (size_t)W.tail) * K * sizeof(T);
+    if (fused && W.r2.bytes < want) {
+      W.drop_graphs();
+      try {
+        W.r2.alloc(want);
+      } catch (const Error& e) {
+        // the extra n x K buffer of a solve that works without it: out of memory here is no failure of the call
+        if (!need_x || e.code != CSGPU_OOM) throw;
+        (void)hipGetLastError();
+        W.r2.release();
+        fused = false;
+        if (knobs().verbose && !W.r2_oom_said) {
+          W.r2_oom_said = true;
+          fprintf(stderr, "csgpu: fused residual update + restriction: no memory for the second residual buffer of a "
+                          "solve that carries the solution, two passes instead\n");
+        }
+      }
+    }
+    if (fused) {
+      int a_, b_, c_;
+      rows = lattice_rupd_restrict_grid<T, K>(H.levels[0].Ql, a_, b_, c_);
+      ++H.fused_restrict_solves;
+    }
+  }
+  if (rows == 0 && release_unused && W.r2.p) {
+    W.drop_graphs();
+    W.r2.release();
+  }
+  return rows;
+}
+
+// work vectors of the enrichment for this batch width
+template <class TP, int K, class Work>
+inline void enrich_prepare(Enrich& EN, Work& W) {
+  if (EN.work_k == K && EN.work_bytes == (int)sizeof(TP)) return;
+  W.drop_graphs();  // (captured chunks hold the old work pointers)
+  enrich_ensure_work<TP, K>(EN);
+}
+
+// z = M^-1 r (r in its V-cycle precision), partials of r'z in fuse.partials. `enrich`: second coarse function on the badly
+// shaped aggregates of a perforated raster lattice (enrich.h): a symmetric multiplicative correction around the V-cycle; its
+// r'z terms travel as kEnrichParts extra rows behind the V-cycle's own `spmv_gp`. Every launch looks at fuse.skip.
+template <class T, class TP, int K>
+inline void apply_preconditioner(Hierarchy<TP>& H, const PcgParams& pp, VcycleFuse<TP>& fuse, const ResidualPingPong<T, TP>& rr,
+                                 TP* z, bool enrich, int spmv_gp, hipStream_t st) {
+  constexpr bool SAME = std::is_same<T, TP>::value;
+  TP* rp = rr.cur_p();
+  fuse.dotw = rp;
+  if (enrich) enrich_pre<TP, K, SAME>(H.enr, rp, fuse.skip, st);
+  // (the fused pass restricted r as the update left it: the pre-pass's change of r follows on the coarse side)
+  if (enrich && fuse.bc_ready) enrich_coarse_fix<TP, K>(H.enr, dptr<TP>(H.levels[1].b), fuse.skip, st);
+  vcycle<TP, K>(H, 0, rp, z, pp.nu_pre, pp.nu_post, pp.nu_coarse, st, &fuse);
+  if (enrich) enrich_post<TP, K, SAME>(H.enr, rp, z, fuse.partials + (size_t)spmv_gp * K, fuse.skip, st);
+}
+
+// ---- the batch solve -----------------------------------------------------------------------------------------------------
+// Every path decision of one pcg_solve, taken by pcg_plan before the first launch. Nothing writes it afterwards but the switch
+// to two passes when polishing begins (PcgRun::polish).
+struct PcgPlan {
+  bool use_dia = false;              // A p from the lattice form, p = z + beta p fused in
+  bool two_product = false;          // level 0 of the V-cycle in its two-product form
+  bool lattice_two_product = false;  // ... on the index-free lattice path
+  bool recompute = false;            // the residual update recomputes A p
+  bool fuse_xa = false;              // the residual update writes the V-cycle's first pre-smoothing sweep
+  bool grounded = false, projected = false, dirichlet = false, enrich = false;
+  bool fused_rr = false;             // the residual update is the fused pass (ResidualPingPong)
+  bool sparse_bc = false, virtual_r0 = false, want_graph = false;
+  int crit0 = 0, nf = 0, chunk = 1, gv = 0, gm = 1;  // gv, gm: launch grids of the vector kernels, of the mask kernels
+  int spmv_g = 0, spmv_gp = 0;       // rows of dot partials the CG product / the last product of the V-cycle write
+  int rz_rows = 0, rr_fused_rows = 0;
+};
+
+// DirichletCoarse. Dirichlet-masked solves run on the hierarchy of the UNGROUNDED Laplacian, and the mode that makes its
+// preconditioned norm optimistic (pcg_plan, crit0) is what makes that preconditioner weak for these solves: along the
+// constant of a connected component the grounded operator has the eigenvalue G / n (G = total conductance between the
+// column's Dirichlet set and the free nodes of the component), the ungrounded hierarchy answers with 1 / shift (fp64) or not
+// at all (fp32: eigenpair dropped, right-hand sides projected), and CG spends its iterations repairing one direction per
+// component (300^2 raster, 8 one-to-all columns: 26 / 51 iterations against 10 for a pair solve). Galerkin along the
+// candidate v_k of component k on the coarsest level gives the exact answer for that direction:
+// v_k'(R A_g P) v_k = 1_k' A_g 1_k = G_k, so the coarsest solve of these solves is
+//     x = pinv_without_the_near_kernel_pairs(b) + sum_k v_k (v_k'b) / G_k.
+// G_k per column comes from a PROBE: the penalty vector d (d_j = conductance from the free nodes to node j of the set) goes
+// down the V-cycle once; every level hands down R (I - A S) d, and v'(R (I - A S) d) = (P v)'d - (A P v)'S d = (P v)'d
+// because A annihilates the candidates -- so the component sums of d arrive at the coarsest level intact and the coarsest
+// solve, in probe mode, writes coef = 1 / G_k instead of solving (no component labels on the fine level, no index structure
+// of the transfer operators needed: the index-free levels serve as they are).
+struct DirichletCoarse {  // (takes the hierarchy out of Dirichlet mode when the solve ends, however it ends)
+  int* mode = nullptr;
+  double** coef = nullptr;
+  ~DirichletCoarse() {
+    if (mode) *mode = 0;
+    if (coef) *coef = nullptr;
+  }
+};
+
+template <class T, class TP, int K>
+inline PcgPlan pcg_plan(const Csr<T>& A, Hierarchy<TP>& H, PcgWork<T, TP>& W, const PcgParams& pp, const Dia<T>* dia) {
+  PcgPlan pl;
   Level<TP>& L0 = H.levels[0];
   const int64_t n = A.nrows;
-  ensure_level_work(H, K);
-  const size_t vbytes = (size_t)n * K * sizeof(T);
-  const bool need_x = pp.need_x;
-  if (need_x && W.x.bytes < vbytes) {
-    W.drop_graphs();
-    W.x.alloc(vbytes);
-  }
-  const bool use_dia = dia && dia->n == n;
-  if (use_dia && W.p2.bytes < (size_t)n * K * sizeof(TP)) {
-    W.drop_graphs();
-    W.p2.alloc((size_t)n * K * sizeof(TP));
-  }
-  T* x = need_x ? dptr<T>(W.x) : nullptr;
-  T* r = dptr<T>(W.r);
-  TP* pbuf[2] = {dptr<TP>(W.p), use_dia ? dptr<TP>(W.p2) : dptr<TP>(W.p)};
-  TP* z = dptr<TP>(W.z);
-  TP* rp = MIXED ? dptr<TP>(W.rp) : (TP*)r;
-  CgScalars* S = dptr<CgScalars>(W.scalars);
-  double* pa = dptr<double>(W.part_a);
-  double* pb = dptr<double>(W.part_b);
-  double* pc = dptr<double>(W.part_c);
-  const int gv = grid_for(n * K);
-  const double atol = pp.atol < 0 ? std::sqrt((double)std::numeric_limits<T>::epsilon()) : pp.atol;
-  const int* orderA = L0.orderA.p ? dptr<int>(L0.orderA) : nullptr;
-  const int nf = need_x ? 0 : W.nf;
-  T* xf = dptr<T>(W.xf);
-  const int* fnode = dptr<int>(W.fnode);
-
-  hipEvent_t e0, e1;
-  CS_HIP(hipEventCreate(&e0));
-  CS_HIP(hipEventCreate(&e1));
-  CS_HIP(hipEventRecord(e0, st));
-
-  // rows of dot partials the CG product / the last product of the V-cycle write (one per workgroup)
-  const bool two_product = H.levels.size() > 1 && L0.two_product() && pp.nu_pre == 1 && pp.nu_post == 1 &&
-                           W.tail >= H.levels[1].A.nrows;
-  const int spmv_g = use_dia ? dia_grid<T, TP, K>(*dia) : spmv_grid<T, K>((int)n);
-  const int spmv_gp = (two_product && L0.lattice_two_product()) ? dia_grid<TP, TP, K>(L0.Sdia)
-                                                                : spmv_grid<TP, K>((int)n);
-  TP* xa0 = dptr<TP>(L0.xa);
-  const TP omega0 = (TP)L0.omega;
-  const bool grounded = pp.gptr && pp.gtotal > 0;
-  const bool projected = pp.proj && pp.proj->nchunks > 0;  // polygons: PCG in the subspace of polygon-wise constants
+  pl.nf = pp.need_x ? 0 : W.nf;
+  pl.use_dia = dia && dia->n == n;
+  pl.two_product = H.levels.size() > 1 && L0.two_product() && pp.nu_pre == 1 && pp.nu_post == 1 &&
+                   W.tail >= H.levels[1].A.nrows;
+  pl.lattice_two_product = pl.two_product && L0.lattice_two_product();
+  pl.gv = grid_for(n * K);
+  pl.spmv_g = pl.use_dia ? dia_grid<T, TP, K>(*dia) : spmv_grid<T, K>((int)n);
+  pl.spmv_gp = pl.lattice_two_product ? dia_grid<TP, TP, K>(L0.Sdia) : spmv_grid<TP, K>((int)n);
+  pl.grounded = pp.gptr && pp.gtotal > 0;
+  pl.projected = pp.proj && pp.proj->nchunks > 0;  // polygons: PCG in the subspace of polygon-wise constants
   // Dirichlet-masked solves run on the hierarchy of the UNGROUNDED Laplacian: its coarsest pseudo-inverse answers the
   // constant vector with a gain of 1 / (regularisation shift), a right-hand side with a non-zero mean (a unit source)
   // then has an astronomically large r0' M^-1 r0, and the reference's relative rule on that norm is met at once (fuzz
   // finding: ||Ax-b||/||b|| = 7e-5 at rtol 1e-10 on a 155-node tree). The reference builds a hierarchy of the grounded
   // matrix, whose preconditioned norm has no such mode (advanced.jl:282-312). These solves therefore must ALSO meet
   // ||r||_2 <= atol + rtol ||b||_2.
-  const int crit0 = (grounded && pp.criterion == CSGPU_CRIT_KRYLOV) ? CSGPU_CRIT_BOTH : pp.criterion;
-  // DirichletCoarse. The same mode is what makes that preconditioner weak for these solves: along the constant of a
-  // connected component the grounded operator has the eigenvalue G / n (G = total conductance between the column's
-  // Dirichlet set and the free nodes of the component), the ungrounded hierarchy answers with 1 / shift (fp64) or not at
-  // all (fp32: eigenpair dropped, right-hand sides projected), and CG spends its iterations repairing one direction per
-  // component (300^2 raster, 8 one-to-all columns: 26 / 51 iterations against 10 for a pair solve). Galerkin along the
-  // candidate v_k of component k on the coarsest level gives the exact answer for that direction:
-  // v_k'(R A_g P) v_k = 1_k' A_g 1_k = G_k, so the coarsest solve of these solves is
-  //     x = pinv_without_the_near_kernel_pairs(b) + sum_k v_k (v_k'b) / G_k.
-  // G_k per column comes from a PROBE: the penalty vector d (d_j = conductance from the free nodes to node j of the set)
-  // goes down the V-cycle once; every level hands down R (I - A S) d, and v'(R (I - A S) d) = (P v)'d - (A P v)'S d =
-  // (P v)'d because A annihilates the candidates -- so the component sums of d arrive at the coarsest level intact and
-  // the coarsest solve, in probe mode, writes coef = 1 / G_k instead of solving (no component labels on the fine level,
-  // no index structure of the transfer operators needed: the index-free levels serve as they are).
-  struct DirichletCoarse {
-    int* mode = nullptr;
-    double** coef = nullptr;
-    ~DirichletCoarse() {
-      if (mode) *mode = 0;
-      if (coef) *coef = nullptr;
-    }
-  } dirichlet_guard;
-  const bool dirichlet = grounded && H.dir_ncomp > 0 && H.coarse_dense && H.coarse_cand.p && A.nnz > 0 && !pp.rhs_in_r;
-  const int gm = grounded ? ceil_div(pp.gtotal, 256) : 1;
+  pl.crit0 = (pl.grounded && pp.criterion == CSGPU_CRIT_KRYLOV) ? CSGPU_CRIT_BOTH : pp.criterion;
+  pl.dirichlet = pl.grounded && H.dir_ncomp > 0 && H.coarse_dense && H.coarse_cand.p && A.nnz > 0 && !pp.rhs_in_r;
+  pl.gm = pl.grounded ? ceil_div(pp.gtotal, 256) : 1;
   // (not with a projection either -- ADVICE r4: r is replaced after the update wrote xa = omega D^-1 r, so the fused first
   // sweep would start the V-cycle from the unprojected residual)
-  const bool fuse_xa = pp.nu_pre >= 1 && H.levels.size() > 1 && !two_product && !grounded && !projected;
+  pl.fuse_xa = pp.nu_pre >= 1 && H.levels.size() > 1 && !pl.two_product && !pl.grounded && !pl.projected;
   // lattice path: the residual update recomputes A p from the lattice form (one read of p, 5 matrix values per row)
   // instead of the product kernel writing A p and the update reading it back (2 x sizeof(T) per vector element)
-  const bool no_recompute = !knobs().recompute_ap;  // A/B knob
-  const bool recompute = use_dia && !fuse_xa && !no_recompute;
+  pl.recompute = pl.use_dia && !pl.fuse_xa && knobs().recompute_ap;  // (A/B knob)
   // A p is stored unless the residual update recomputes it; the explicit post-check of a carried solution uses the
   // buffer too. b is read unless the caller wrote the right-hand side straight into r.
-  T* Ap = (!recompute || need_x) ? W.need_vec(W.Ap) : (T*)nullptr;
-  const T* b = pp.rhs_in_r ? (const T*)nullptr : (const T*)W.need_vec(W.b);
-  VcycleFuse<TP> fuse;
-  fuse.b_has_tail = two_product;
-  fuse.dotw = rp;
-  fuse.partials = pa;
-  // second coarse function on the badly shaped aggregates of a perforated raster lattice (enrich.h): a symmetric
-  // multiplicative correction around the V-cycle; its r'z terms travel as kEnrichParts extra rows behind the V-cycle's own
-  Enrich& EN = H.enr;
-  // (Dirichlet-masked solves keep it: with Pm the mask, the preconditioner in effect is Pm M Pm -- r is zero at the grounded
-  // entries and z is masked after the correction, so symmetry and the r'z terms hold; polygon handles -- `projected` -- do
-  // not use it: their hierarchy's matrix carries the strengthened interiors)
-  const bool enrich = enrich_applicable<TP>(EN, n, use_dia && two_product && L0.lattice_two_product(), projected);
-  // Fused residual update + restriction (lattice.h, Knobs::fused_restrict): r_new = r - alpha A p and b_c = Q^T r_new in one
-  // pass. The residual then ping-pongs between W.r and W.r2 -- `r` / `rp` below are re-pointed after every fused launch and
-  // `rsel` (which buffer holds the current residual) is part of the graph key. One precision only (the V-cycle reads r
-  // itself), solves without masks or projections (which touch r between the update and the cycle). An
-  // ENRICHED level takes it when the set-up built W = Q'AE (EN.ntouch > 0): enrich_pre changes r on its halo cells after
-  // the pass has restricted it, and enrich_coarse_fix applies the restriction's share of that change to b_c (enrich.h).
-  // A solve that carries the whole solution takes it only when asked to (Knobs::fused_restrict = 1): the pass then also
-  // runs x += alpha p on the cells it owns (the XUP form of the kernel), and W.r2 comes ON TOP of x, b and A p -- the
-  // default leaves such a solve's device memory as it was.
-  bool fused_rr = false;
-  T* rbuf[2] = {r, nullptr};
-  int rsel = 0;
-  if constexpr (!MIXED && lattice_rupd_restrict_fits<T, K>()) {
-    fused_rr = fused_restrict_wanted<T>() && recompute && two_product && L0.lattice_two_product() &&
-               (!need_x || knobs().fused_restrict > 0) && !grounded && !projected && (!enrich || EN.ntouch > 0) &&
-               pp.nu_pre == 1 && pp.nu_post == 1;
-    if (fused_rr) {
-      const size_t want = ((size_t)n + (size_t)W.tail) * K * sizeof(T);
-      if (W.r2.bytes < want) {
-        W.drop_graphs();
-        if (need_x) {
-          // the extra n x K buffer of a solve that works without it: out of memory here is no failure of the call
-          try {
-            W.r2.alloc(want);
-          } catch (const Error& e) {
-            if (e.code != CSGPU_OOM) throw;
-            (void)hipGetLastError();
-            W.r2.release();
-            fused_rr = false;
-            if (knobs().verbose && !W.r2_oom_said) {
-              W.r2_oom_said = true;
-              fprintf(stderr, "csgpu: fused residual update + restriction: no memory for the second residual buffer of a "
-                              "solve that carries the solution, two passes instead\n");
-            }
-          }
-        } else {
-          W.r2.alloc(want);
-        }
-      }
-    }
-    if (fused_rr) {
-      rbuf[1] = dptr<T>(W.r2);
-      ++H.fused_restrict_solves;
-    }
-  }
-  if (!fused_rr && W.r2.p) {  // (a solve that carries x, b and A p: give the second residual buffer back first)
-    W.drop_graphs();
-    W.r2.release();
-  }
+  if (!pl.recompute || pp.need_x) W.need_vec(W.Ap);
+  if (!pp.rhs_in_r) W.need_vec(W.b);
+  // (Dirichlet-masked solves keep the enrichment: with Pm the mask, the preconditioner in effect is Pm M Pm -- r is zero at
+  // the grounded entries and z is masked after the correction, so symmetry and the r'z terms hold; polygon handles --
+  // `projected` -- do not use it: their hierarchy's matrix carries the strengthened interiors)
+  pl.enrich = enrich_applicable<TP>(H.enr, n, pl.use_dia && pl.lattice_two_product, pl.projected);
+  pl.rr_fused_rows = acquire_fused_residual<T, TP, K>(H, W, pp, n, pl.enrich, pl.recompute, pl.lattice_two_product, pp.need_x,
+                                                      pl.grounded || pl.projected, true);
+  pl.fused_rr = pl.rr_fused_rows > 0;
   // pair solves on the lattice two-product path (see PcgParams::pair_src): the first restriction is a scatter of the pairs'
   // <= 18 entries per column -- any precision, any batch width -- and on the fused path r0 is never stored at all
   // (an enriched level on the fused path takes the scatter too -- the pre-pass's share follows on the coarse side, exactly as
   // after a fused update, so a column's first cycle sees the same b_c here and in the streaming loop -- but r0 itself is
   // stored: the pre-pass reads it)
-  const bool sparse_bc = pp.pair_src && pp.rhs_in_r && knobs().sparse_init && use_dia && two_product &&
-                         L0.lattice_two_product() && !grounded && !projected && (!enrich || fused_rr);
-  const bool virtual_r0 = sparse_bc && fused_rr && pp.bb_host && !enrich;
-  if (enrich && (EN.work_k != K || EN.work_bytes != (int)sizeof(TP))) {
-    W.drop_graphs();  // (captured chunks hold the old work pointers)
-    enrich_ensure_work<TP, K>(EN);
-  }
-  const int rz_rows = spmv_gp + (enrich ? kEnrichParts : 0);
-  auto precondition = [&](const int* skip_flag) {   // z = M^-1 r (r in its V-cycle precision: rp), partials of r'z in pa
-    if (enrich) enrich_pre<TP, K, !MIXED>(EN, rp, skip_flag, st);
-    // (the fused pass restricted r as the update left it: the pre-pass's change of r follows on the coarse side)
-    if (enrich && fuse.bc_ready) enrich_coarse_fix<TP, K>(EN, dptr<TP>(H.levels[1].b), skip_flag, st);
-    vcycle<TP, K>(H, 0, rp, z, pp.nu_pre, pp.nu_post, pp.nu_coarse, st, &fuse);
-    if (enrich) enrich_post<TP, K, !MIXED>(EN, rp, z, pa + (size_t)spmv_gp * K, skip_flag, st);
-  };
-
-  if (dirichlet) {
-    const size_t cbytes = (size_t)kMaxDirComp * kMaxK * sizeof(double);
-    if (W.dir_coef.bytes < cbytes) W.dir_coef.alloc(cbytes);
-    double* coef = dptr<double>(W.dir_coef);
-    TP* mark = pbuf[0];  // free until the first iteration; rp (the V-cycle's input, with its tail) takes the penalty vector
-    CS_HIP(hipMemsetAsync(mark, 0, (size_t)n * K * sizeof(TP), st));
-    CS_HIP(hipMemsetAsync(rp, 0, (size_t)n * K * sizeof(TP), st));
-    CS_HIP(hipMemsetAsync(coef, 0, cbytes, st));
-    hipLaunchKernelGGL((mark_grounds_kernel<TP, K>), dim3(gm), dim3(256), 0, st, pp.gptr, pp.gidx, mark);
-    hipLaunchKernelGGL((dirichlet_penalty_kernel<T, TP, K>), dim3(gm), dim3(256), 0, st, A.rp(), A.ci(), A.va(), pp.gptr,
-                       pp.gidx, (const TP*)mark, rp);
-    H.dir_coef = coef;
-    H.dir_mode = 2;
-    dirichlet_guard.mode = &H.dir_mode;
-    dirichlet_guard.coef = &H.dir_coef;
-    vcycle<TP, K>(H, 0, rp, z, pp.nu_pre, pp.nu_post, pp.nu_coarse, st, &fuse);
-    H.dir_mode = 1;
-    check_launch("pcg dirichlet probe");
-  }
-  if (need_x) CS_HIP(hipMemsetAsync(x, 0, vbytes, st));
-  if (nf > 0) CS_HIP(hipMemsetAsync(xf, 0, (size_t)nf * K * sizeof(T), st));
-  W.have_x = need_x;
-  CS_REQUIRE(!(pp.rhs_in_r && need_x), CSGPU_INTERNAL, "rhs_in_r needs the focal-node path");
-  if (!pp.rhs_in_r) CS_HIP(hipMemcpyAsync(r, b, vbytes, hipMemcpyDeviceToDevice, st));
-  CS_HIP(hipMemsetAsync(S, 0, sizeof(CgScalars), st));
-  bool rp_written = pp.rhs_in_r && pp.rp_ready;
-  if (pp.rhs_in_r && pp.pair_src && !virtual_r0) {  // r0 = e_dst - e_src, in both precisions
-    CS_HIP(hipMemsetAsync(r, 0, vbytes, st));
-    hipLaunchKernelGGL((pairs_rhs_kernel<T, K>), dim3(1), dim3(64), 0, st, r, pp.pair_src, pp.pair_dst, pp.pair_cols);
-    if (MIXED) {
-      CS_HIP(hipMemsetAsync(rp, 0, (size_t)n * K * sizeof(TP), st));
-      hipLaunchKernelGGL((pairs_rhs_kernel<TP, K>), dim3(1), dim3(64), 0, st, rp, pp.pair_src, pp.pair_dst, pp.pair_cols);
-    }
-    rp_written = true;
-  }
-  if (MIXED && !rp_written)
-    hipLaunchKernelGGL((convert_kernel<T, TP>), dim3(gv), dim3(256), 0, st, n * K, (const T*)r, rp);
-  // polygons: r0 = Pi b (a unit current into a polygon node is spread evenly over the polygon's cells)
-  if (projected) poly_project<T, TP, K>(*pp.proj, r, MIXED ? rp : (TP*)nullptr, (const int*)nullptr, st);
-  // z = M^-1 r with the partials of r'z fused into the last smoothing product; r'r separately (criterion 1 / init)
-  if (sparse_bc) {
-    lattice_restrict_pairs<TP, K>(L0.Ql, pp.pair_src, pp.pair_dst, pp.pair_cols, dptr<TP>(H.levels[1].b), st);
-    fuse.bc_ready = true;
-    if (virtual_r0) {
-      ++H.virtual_rhs_solves;
-      fuse.pair_src = pp.pair_src;
-      fuse.pair_dst = pp.pair_dst;
-      fuse.pair_cols = pp.pair_cols;
-    }
-  }
-  precondition(nullptr);
-  fuse.bc_ready = false;
-  fuse.pair_src = fuse.pair_dst = nullptr;
-  // (the fused r'z partials are those of the projected z too: r is in the subspace, r'z = r'(Pi z))
-  if (projected) poly_project<TP, TP, K>(*pp.proj, z, (TP*)nullptr, (const int*)nullptr, st);
-  // (the fused r'z partials are unaffected by masking z afterwards: r is zero at the grounded entries)
-  if (grounded)
-    hipLaunchKernelGGL((mask_grounds_kernel<TP, TP, K>), dim3(gm), dim3(256), 0, st, pp.gptr, pp.gidx, z, (TP*)nullptr,
-                       (const int*)nullptr);
-  int rr_rows = gv;  // rows of r'r partials currently in pb
-  if (pp.rhs_in_r && pp.bb_host) {
-    CS_HIP(hipMemcpyAsync(pb, pp.bb_host, (size_t)K * sizeof(double), hipMemcpyHostToDevice, st));
-    rr_rows = 1;
-  } else {
-    hipLaunchKernelGGL((dot_kernel<T, K, false>), dim3(gv), dim3(256), 0, st, n, (const T*)r, (const T*)r, pb,
-                       (const T*)nullptr, (const T*)nullptr, (double*)nullptr);
-  }
-  // partial rows of the big SpMM-shaped launches are collapsed before the single-workgroup scalar kernels read them
-  double* pac = dptr<double>(W.part_ca);
-  double* pcc = dptr<double>(W.part_cc);
-  // (Knobs::collapse_min: test knob, so that a test can exercise the path on a small problem)
-  const int collapse_min = knobs().collapse_min >= 0 ? (int)std::max<int64_t>(1, knobs().collapse_min) : 4 * kCollapsedParts;
-  auto collapsed = [&](double* src, int nparts, double* dst) -> std::pair<const double*, int> {
-    if (nparts <= collapse_min) return {src, nparts};
-    hipLaunchKernelGGL((collapse_partials_kernel<K>), dim3(ceil_div(kCollapsedParts * K, 256)), dim3(256), 0, st,
-                       (const double*)src, nparts, dst);
-    return {dst, kCollapsedParts};
-  };
-  {
-    auto rz = collapsed(pa, rz_rows, pac);
-    hipLaunchKernelGGL((cg_beta_kernel<K>), dim3(1), dim3(256), 0, st, S, rz.first, rz.second, (const double*)pb, rr_rows,
-                       crit0, pp.rtol, atol, 1, ncols_active);
-  }
-  // the first iteration runs p = z + beta p with beta = 0 (set by the init call above): the lattice product takes p = z
-  // whatever the old p holds (stencil.h), the CSR path's update kernel multiplies the old p by zero and needs it finite
-  if (!use_dia) CS_HIP(hipMemsetAsync(pbuf[0], 0, (size_t)n * K * sizeof(TP), st));
-  check_launch("pcg init");
-
-  int host_done = 0;
-  CS_HIP(hipMemcpyAsync(&host_done, &S->all_done, sizeof(int), hipMemcpyDeviceToHost, st));
-  CS_HIP(hipStreamSynchronize(st));
-  bool r0_consumed = false;
-  if (virtual_r0 && host_done) {
-    // nothing will iterate (every column's right-hand side is zero): the post-check reads r, so store r0 after all
-    CS_HIP(hipMemsetAsync(r, 0, vbytes, st));
-    hipLaunchKernelGGL((pairs_rhs_kernel<T, K>), dim3(1), dim3(64), 0, st, r, pp.pair_src, pp.pair_dst, pp.pair_cols);
-    r0_consumed = true;
-  }
-
-  const int max_timed = knobs().timed_launches;  // per solve
-  int timed = 0;
-  int it = 0;
-  int graph_launches = 0;
-  int parity = 0;  // pbuf[parity] holds the current search direction (stencil path: ping-pong; CSR path: one buffer)
-  int rr_fused_rows = 0;  // rows of r'r partials the fused update wrote (one per workgroup)
-  if constexpr (!MIXED && lattice_rupd_restrict_fits<T, K>()) {
-    int a_, b_, c_;
-    if (fused_rr) rr_fused_rows = lattice_rupd_restrict_grid<T, K>(L0.Ql, a_, b_, c_);
-  }
-  fuse.xa_ready = fuse_xa;
-  fuse.skip = &S->all_done;
-  int criterion = crit0;  // switches to the true residual for the polishing phase (below)
-  // one PCG iteration as a sequence of launches on `st` (no host interaction: this is what gets captured)
-  //   p = z + beta p ; Ap = A p, p'Ap ; alpha ; r -= alpha Ap, x += alpha p ; z = M^-1 r, r'z ; beta, stopping rule
-  // The first product of a batch on the lattice path: beta = 0 for every column (the init call above), so the kernel takes
-  // p = z and is not handed the old search direction at all -- a third of the launch's vector traffic, once per batch. That
-  // launch (and its iteration's residual update) stays out of the timed set: cg_spmv_ms / cg_spmv_bytes describe launches of
-  // ONE size.
-  bool first_product = use_dia;
-  auto iteration = [&](bool time_it) {
-    const bool short_first = first_product;
-    first_product = false;
-    const TP* pin = short_first ? (const TP*)nullptr : (const TP*)pbuf[parity];
-    TP* pcur = use_dia ? pbuf[parity ^ 1] : pbuf[parity];
-    time_it = time_it && timed < max_timed && !short_first;
-    const int tslot = timed;
-    auto ev_begin = [&]() {
-      if (!time_it) return;
-      while ((int)W.ev.size() < 2 * (timed + 1) || (int)W.ev2.size() < 2 * (timed + 1)) {
-        hipEvent_t ea, eb;
-        CS_HIP(hipEventCreate(&ea));
-        CS_HIP(hipEventCreate(&eb));
-        auto& v = (int)W.ev.size() < 2 * (timed + 1) ? W.ev : W.ev2;
-        v.push_back(ea);
-        v.push_back(eb);
-      }
-      CS_HIP(hipEventRecord(W.ev[2 * timed], st));
-    };
-    auto ev_end = [&]() {
-      if (!time_it) return;
-      CS_HIP(hipEventRecord(W.ev[2 * timed + 1], st));
-      ++timed;
-    };
-    if (use_dia) {
-      // fused: p = z + beta p (written to the other buffer), Ap = A p, partials of p'Ap
-      ev_begin();
-      dia_cg_product<T, TP, K>(*dia, (const CgScalars*)S, (const TP*)z, pin, pcur, recompute ? (T*)nullptr : Ap, pc, st);
-      ev_end();
-      parity ^= 1;
-    } else {
-      hipLaunchKernelGGL((cg_update_p_kernel<T, TP, K>), dim3(gv), dim3(256), 0, st, n, (const CgScalars*)S, pin, pcur,
-                         (const TP*)z);
-      SpmvArgs<T, TP> a = spmv_args<T, TP>(A, (const TP*)pcur, Ap);
-      a.order = orderA;
-      a.skip = &S->all_done;
-      a.dotw = nullptr;  // dot with x itself: p'Ap
-      a.partials = pc;
-      ev_begin();
-      spmv_launch_cg<T, K, TP>(a, st);
-      ev_end();
-    }
-    {
-      auto pap = collapsed(pc, spmv_g, pcc);
-      hipLaunchKernelGGL((cg_alpha_kernel<K>), dim3(1), dim3(256), 0, st, S, pap.first, pap.second);
-    }
-    // r -= alpha Ap (+ x += alpha p when the whole solution is wanted), fused with the TP copy of r, the level-0 first
-    // pre-smoothing sweep xa = omega D^-1 r and (when the true residual is monitored) the partials of r'r
-    if (time_it && use_dia) CS_HIP(hipEventRecord(W.ev2[2 * tslot], st));
-    if (recompute) {
-      // (the partials of r'r come for free here; the focal path's post-check reads the last ones instead of making
-      // another pass over r)
-      if (fused_rr) {
-        if constexpr (!MIXED) {
-          T* rnew = rbuf[rsel ^ 1];
-          const bool first = virtual_r0 && !r0_consumed;  // (r holds nothing yet: the kernel synthesises r0)
-          rr_fused_rows = lattice_rupd_restrict<T, K>(*dia, L0.Ql, (const CgScalars*)S, (const T*)pcur, (const T*)r, rnew,
-                                                      dptr<T>(H.levels[1].b), pb, st, nullptr, nullptr, nullptr,
-                                                      first ? pp.pair_src : nullptr, need_x ? nullptr : pp.pair_dst,
-                                                      pp.pair_cols, x);
-          r0_consumed = true;
-          rsel ^= 1;
-          r = rnew;
-          rp = (TP*)rnew;
-          fuse.dotw = rp;
-        }
-      } else {
-        dia_residual_update<T, TP, K>(*dia, (const CgScalars*)S, (const TP*)pcur, r, MIXED ? rp : (TP*)nullptr, x, pb, st);
-      }
-    } else {
-      TP* rpo = MIXED ? rp : (TP*)nullptr;
-      TP* xao = fuse_xa ? xa0 : (TP*)nullptr;
-      const TP* dinv0 = dptr<TP>(L0.dinv);
-      const bool rr = criterion != CSGPU_CRIT_KRYLOV;
-#define CS_UPD_R(RR, XUP)                                                                                              \
-  hipLaunchKernelGGL((cg_update_r_kernel<T, TP, K, RR, XUP>), dim3(gv), dim3(256), 0, st, n, (const CgScalars*)S, r,    \
-                     (const T*)Ap, rpo, xao, dinv0, omega0, pb, x, (const TP*)pcur)
-      if (rr && need_x) CS_UPD_R(true, true);
-      else if (rr) CS_UPD_R(true, false);
-      else if (need_x) CS_UPD_R(false, true);
-      else CS_UPD_R(false, false);
-#undef CS_UPD_R
-    }
-    if (time_it && use_dia) CS_HIP(hipEventRecord(W.ev2[2 * tslot + 1], st));
-    const bool rr_after_mask = (grounded || projected) && criterion != CSGPU_CRIT_KRYLOV;
-    if (projected) {  // r <- Pi r: the residual of the projected system (both precisions)
-      poly_project<T, TP, K>(*pp.proj, r, MIXED ? rp : (TP*)nullptr, (const int*)&S->all_done, st);
-      if (rr_after_mask) {
-        // ||r||^2 in NODE space = the merged system's (the reference's figure): cell-space partials + one correction row
-        hipLaunchKernelGGL((dot_kernel<T, K, false>), dim3(gv), dim3(256), 0, st, n, (const T*)r, (const T*)r, pb,
-                           (const T*)nullptr, (const T*)nullptr, (double*)nullptr);
-        hipLaunchKernelGGL((poly_norm_corr_kernel<K>), dim3(1), dim3(256), 0, st, *pp.proj, pb + (size_t)gv * K,
-                           (const int*)&S->all_done);
-      }
-    }
-    if (grounded) {  // the update put (A p) at the grounded rows into r: back to zero, in both precisions
-      hipLaunchKernelGGL((mask_grounds_kernel<T, TP, K>), dim3(gm), dim3(256), 0, st, pp.gptr, pp.gidx, r,
-                         MIXED ? rp : (TP*)nullptr, (const int*)&S->all_done);
-      // the partials of r'r the update wrote include alpha (A p) at the Dirichlet rows, which are not equations of the
-      // reduced system (ADVICE r2): when the true residual is monitored, take the norm of the masked r instead
-      if (rr_after_mask)
-        hipLaunchKernelGGL((dot_kernel<T, K, false>), dim3(gv), dim3(256), 0, st, n, (const T*)r, (const T*)r, pb,
-                           (const T*)nullptr, (const T*)nullptr, (double*)nullptr);
-    }
-    if (nf > 0)
-      hipLaunchKernelGGL((cg_focal_x_kernel<T, TP, K>), dim3(ceil_div(nf * K, 256)), dim3(256), 0, st, (const CgScalars*)S,
-                         fnode, nf, (const TP*)pcur, xf);
-    fuse.bc_ready = fused_rr;
-    precondition((const int*)&S->all_done);
-    fuse.bc_ready = false;
-    if (projected) poly_project<TP, TP, K>(*pp.proj, z, (TP*)nullptr, (const int*)&S->all_done, st);
-    if (grounded)
-      hipLaunchKernelGGL((mask_grounds_kernel<TP, TP, K>), dim3(gm), dim3(256), 0, st, pp.gptr, pp.gidx, z, (TP*)nullptr,
-                         (const int*)&S->all_done);
-    {
-      auto rz = collapsed(pa, rz_rows, pac);
-      // r'r partials (true-residual criterion): one row per workgroup of whichever kernel updated r
-      const double* prr = pb;
-      int nrr = (projected && rr_after_mask) ? gv + 1 : gv;   // (+ the node-space correction row of a polygon handle)
-      if (recompute && criterion != CSGPU_CRIT_KRYLOV && !rr_after_mask) {
-        auto rr = collapsed(pb, fused_rr ? rr_fused_rows : spmv_g, pcc);
-        prr = rr.first;
-        nrr = rr.second;
-      }
-      hipLaunchKernelGGL((cg_beta_kernel<K>), dim3(1), dim3(256), 0, st, S, rz.first, rz.second, prr, nrr, criterion,
-                         pp.rtol, atol, 0, ncols_active);
-    }
-  };
-
+  pl.sparse_bc = pp.pair_src && pp.rhs_in_r && knobs().sparse_init && pl.use_dia && pl.lattice_two_product && !pl.grounded &&
+                 !pl.projected && (!pl.enrich || pl.fused_rr);
+  pl.virtual_r0 = pl.sparse_bc && pl.fused_rr && pp.bb_host && !pl.enrich;
+  if (pl.enrich) enrich_prepare<TP, K>(H.enr, W);
+  pl.rz_rows = pl.spmv_gp + (pl.enrich ? kEnrichParts : 0);
   // Launch-bound regime (small rasters: ~75 launches of a few microseconds each per iteration): replay a captured
   // hipGraph of `check_every` iterations instead of issuing the launches one by one. The first chunk always runs
   // directly (it is the one the SpMV timing events sit in); every device-side early-out (skip flag) works unchanged
   // inside the graph because it lives in device memory.
-  const int chunk = std::max(1, pp.check_every);
-  const bool want_graph = !W.graph_broken && !(use_dia && (chunk & 1)) &&
-                          (pp.use_graph > 0 || (pp.use_graph == 0 && (int64_t)n * K <= ((int64_t)1 << 25)));
-  PcgGraphKey gkey;
-  gkey.K = K;
-  gkey.ncols_active = ncols_active;
-  gkey.criterion = criterion;
-  gkey.nu_pre = pp.nu_pre;
-  gkey.nu_post = pp.nu_post;
-  gkey.nu_coarse = pp.nu_coarse;
-  gkey.iters = chunk;
-  gkey.rtol = pp.rtol;
-  gkey.atol = atol;
-  gkey.matrix = (const void*)A.val.p;
-  gkey.need_x = need_x ? 1 : 0;
-  gkey.nf = nf;
-  gkey.gptr = grounded ? (const void*)pp.gptr : nullptr;
-  gkey.gidx = grounded ? (const void*)pp.gidx : nullptr;
-  gkey.gtotal = grounded ? pp.gtotal : 0;
-  gkey.proj = projected ? (const void*)pp.proj->cells : nullptr;
-  auto chunk_graph = [&]() -> hipGraphExec_t {
+  pl.chunk = std::max(1, pp.check_every);
+  pl.want_graph = !W.graph_broken && !(pl.use_dia && (pl.chunk & 1)) &&
+                  (pp.use_graph > 0 || (pp.use_graph == 0 && (int64_t)n * K <= ((int64_t)1 << 25)));
+  return pl;
+}
+
+// One pcg_solve: what it was called with, its plan and buffers, and the state its phases advance.
+template <class T, class TP, int K>
+struct PcgRun {
+  static constexpr bool MIXED = !std::is_same<T, TP>::value;
+  const Csr<T>& A;
+  Hierarchy<TP>& H;
+  PcgWork<T, TP>& W;
+  const PcgParams& pp;
+  const Dia<T>* dia;
+  int ncols_active;
+  hipStream_t st;
+  int64_t n;  // A.nrows
+  PcgPtrs<T, TP> w;
+  PcgPlan plan;
+  T* x = pp.need_x ? dptr<T>(W.x) : nullptr;
+  T* Ap = (!plan.recompute || pp.need_x) ? dptr<T>(W.Ap) : nullptr;
+  const T* b = pp.rhs_in_r ? nullptr : dptr<T>(W.b);
+  T* xf = dptr<T>(W.xf);
+  const int* fnode = dptr<int>(W.fnode);
+  VcycleFuse<TP> fuse;
+  DirichletCoarse dirichlet_guard;
+  ResidualPingPong<T, TP> resid{{w.r, plan.fused_rr ? dptr<T>(W.r2) : nullptr}, w.rp};
+  int it = 0, host_done = 0;
+  int parity = 0;              // w.pbuf[parity] holds the current search direction (stencil path: ping-pong; CSR path: one buffer)
+  int criterion = plan.crit0;  // switches to the true residual for the polishing phase
+  int timed = 0, graph_launches = 0;
+  // The first product of a batch on the lattice path: beta = 0 for every column (the init call of setup()), so the kernel
+  // takes p = z and is not handed the old search direction at all -- a third of the launch's vector traffic, once per batch.
+  // That launch (and its iteration's residual update) stays out of the timed set: cg_spmv_ms / cg_spmv_bytes describe
+  // launches of ONE size.
+  bool first_product = plan.use_dia;
+  bool r0_consumed = false;  // virtual_r0: the first fused update has synthesised r0 (or setup() stored it after all)
+  PcgBatchResult res;
+
+  int real_updates() const {  // launches enqueued after every column had stopped return at once (device flag)
+    int real = 0;
+    for (int c = 0; c < ncols_active && c < kMaxK; ++c) real = std::max(real, res.s.iters[c]);
+    return real;
+  }
+  std::pair<const double*, int> collapsed(double* src, int nparts, double* dst) const {
+    return collapse_partials<K>(src, nparts, dst, w.collapse_min, st);
+  }
+
+  // z = M^-1 r in the subspace of the solve, partials of r'z in w.pa; every launch looks at fuse.skip
+  void precondition() {
+    apply_preconditioner<T, TP, K>(H, pp, fuse, resid, w.z, plan.enrich, plan.spmv_gp, st);
+    fuse.bc_ready = false;
+    // (the fused r'z partials are those of the projected z too: r is in the subspace, r'z = r'(Pi z))
+    if (plan.projected) poly_project<TP, TP, K>(*pp.proj, w.z, (TP*)nullptr, fuse.skip, st);
+    // (the fused r'z partials are unaffected by masking z afterwards: r is zero at the grounded entries)
+    if (plan.grounded)
+      hipLaunchKernelGGL((mask_grounds_kernel<TP, TP, K>), dim3(plan.gm), dim3(256), 0, st, pp.gptr, pp.gidx, w.z, (TP*)nullptr,
+                         fuse.skip);
+  }
+
+  // r0, z0 = M^-1 r0 and the scalars of iteration 0 (with the Dirichlet probe in front); leaves host_done
+  void setup() {
+    const size_t vbytes = (size_t)n * K * sizeof(T);
+    T* r = w.r;
+    TP* rp = w.rp;
+    if (plan.dirichlet) {
+      const size_t cbytes = (size_t)kMaxDirComp * kMaxK * sizeof(double);
+      if (W.dir_coef.bytes < cbytes) W.dir_coef.alloc(cbytes);
+      double* coef = dptr<double>(W.dir_coef);
+      TP* mark = w.pbuf[0];  // free until the first iteration; rp (the V-cycle's input, with its tail) takes the penalty vector
+      CS_HIP(hipMemsetAsync(mark, 0, (size_t)n * K * sizeof(TP), st));
+      CS_HIP(hipMemsetAsync(rp, 0, (size_t)n * K * sizeof(TP), st));
+      CS_HIP(hipMemsetAsync(coef, 0, cbytes, st));
+      hipLaunchKernelGGL((mark_grounds_kernel<TP, K>), dim3(plan.gm), dim3(256), 0, st, pp.gptr, pp.gidx, mark);
+      hipLaunchKernelGGL((dirichlet_penalty_kernel<T, TP, K>), dim3(plan.gm), dim3(256), 0, st, A.rp(), A.ci(), A.va(), pp.gptr,
+                         pp.gidx, (const TP*)mark, rp);
+      H.dir_coef = coef;
+      H.dir_mode = 2;
+      dirichlet_guard.mode = &H.dir_mode;
+      dirichlet_guard.coef = &H.dir_coef;
+      apply_preconditioner<T, TP, K>(H, pp, fuse, resid, w.z, false, plan.spmv_gp, st);  // (the probe: the V-cycle alone)
+      H.dir_mode = 1;
+      check_launch("pcg dirichlet probe");
+    }
+    if (pp.need_x) CS_HIP(hipMemsetAsync(x, 0, vbytes, st));
+    if (plan.nf > 0) CS_HIP(hipMemsetAsync(xf, 0, (size_t)plan.nf * K * sizeof(T), st));
+    W.have_x = pp.need_x;
+    CS_REQUIRE(!(pp.rhs_in_r && pp.need_x), CSGPU_INTERNAL, "rhs_in_r needs the focal-node path");
+    if (!pp.rhs_in_r) CS_HIP(hipMemcpyAsync(r, b, vbytes, hipMemcpyDeviceToDevice, st));
+    CS_HIP(hipMemsetAsync(w.S, 0, sizeof(CgScalars), st));
+    auto store_pair_rhs = [&]() {  // r0 = e_dst - e_src
+      CS_HIP(hipMemsetAsync(r, 0, vbytes, st));
+      hipLaunchKernelGGL((pairs_rhs_kernel<T, K>), dim3(1), dim3(64), 0, st, r, pp.pair_src, pp.pair_dst, pp.pair_cols);
+    };
+    bool rp_written = pp.rhs_in_r && pp.rp_ready;
+    if (pp.rhs_in_r && pp.pair_src && !plan.virtual_r0) {  // ... in both precisions
+      store_pair_rhs();
+      if (MIXED) {
+        CS_HIP(hipMemsetAsync(rp, 0, (size_t)n * K * sizeof(TP), st));
+        hipLaunchKernelGGL((pairs_rhs_kernel<TP, K>), dim3(1), dim3(64), 0, st, rp, pp.pair_src, pp.pair_dst, pp.pair_cols);
+      }
+      rp_written = true;
+    }
+    if (MIXED && !rp_written)
+      hipLaunchKernelGGL((convert_kernel<T, TP>), dim3(plan.gv), dim3(256), 0, st, n * K, (const T*)r, rp);
+    // polygons: r0 = Pi b (a unit current into a polygon node is spread evenly over the polygon's cells)
+    if (plan.projected) poly_project<T, TP, K>(*pp.proj, r, MIXED ? rp : (TP*)nullptr, (const int*)nullptr, st);
+    // z = M^-1 r with the partials of r'z fused into the last smoothing product; r'r separately (criterion 1 / init)
+    if (plan.sparse_bc) {
+      lattice_restrict_pairs<TP, K>(H.levels[0].Ql, pp.pair_src, pp.pair_dst, pp.pair_cols, dptr<TP>(H.levels[1].b), st);
+      fuse.bc_ready = true;
+      if (plan.virtual_r0) {
+        ++H.virtual_rhs_solves;
+        fuse.pair_src = pp.pair_src;
+        fuse.pair_dst = pp.pair_dst;
+        fuse.pair_cols = pp.pair_cols;
+      }
+    }
+    precondition();
+    fuse.pair_src = fuse.pair_dst = nullptr;
+    int rr_rows = plan.gv;  // rows of r'r partials currently in pb
+    if (pp.rhs_in_r && pp.bb_host) {
+      CS_HIP(hipMemcpyAsync(w.pb, pp.bb_host, (size_t)K * sizeof(double), hipMemcpyHostToDevice, st));
+      rr_rows = 1;
+    } else {
+      hipLaunchKernelGGL((dot_kernel<T, K, false>), dim3(plan.gv), dim3(256), 0, st, n, (const T*)r, (const T*)r, w.pb,
+                         (const T*)nullptr, (const T*)nullptr, (double*)nullptr);
+    }
+    auto rz = collapsed(w.pa, plan.rz_rows, w.pac);
+    hipLaunchKernelGGL((cg_beta_kernel<K>), dim3(1), dim3(256), 0, st, w.S, rz.first, rz.second, (const double*)w.pb, rr_rows,
+                       plan.crit0, pp.rtol, w.atol, 1, ncols_active);
+    // the first iteration runs p = z + beta p with beta = 0 (set by the init call above): the lattice product takes p = z
+    // whatever the old p holds (stencil.h), the CSR path's update kernel multiplies the old p by zero and needs it finite
+    if (!plan.use_dia) CS_HIP(hipMemsetAsync(w.pbuf[0], 0, (size_t)n * K * sizeof(TP), st));
+    check_launch("pcg init");
+    CS_HIP(hipMemcpyAsync(&host_done, &w.S->all_done, sizeof(int), hipMemcpyDeviceToHost, st));
+    CS_HIP(hipStreamSynchronize(st));
+    if (plan.virtual_r0 && host_done) {
+      // nothing will iterate (every column's right-hand side is zero): the post-check reads r, so store r0 after all
+      store_pair_rhs();
+      r0_consumed = true;
+    }
+    fuse.xa_ready = plan.fuse_xa;
+    fuse.skip = &w.S->all_done;
+  }
+
+  // one PCG iteration as a sequence of launches on the stream (no host interaction: this is what gets captured)
+  //   p = z + beta p ; Ap = A p, p'Ap ; alpha ; r -= alpha Ap, x += alpha p ; z = M^-1 r, r'z ; beta, stopping rule
+  void iteration(bool time_it) {
+    Level<TP>& L0 = H.levels[0];
+    const int gv = plan.gv;
+    const CgScalars* S = w.S;
+    const int* done = &w.S->all_done;
+    const bool short_first = first_product;
+    first_product = false;
+    const TP* pin = short_first ? (const TP*)nullptr : (const TP*)w.pbuf[parity];
+    TP* pcur = plan.use_dia ? w.pbuf[parity ^ 1] : w.pbuf[parity];
+    time_it = time_it && timed < knobs().timed_launches && !short_first;  // (timed_launches: per solve)
+    const int slot = timed;
+    if (plan.use_dia) {
+      // fused: p = z + beta p (written to the other buffer), Ap = A p, partials of p'Ap
+      if (time_it) W.ev.begin(slot, st);
+      dia_cg_product<T, TP, K>(*dia, S, (const TP*)w.z, pin, pcur, plan.recompute ? (T*)nullptr : Ap, w.pc, st);
+      parity ^= 1;
+    } else {
+      hipLaunchKernelGGL((cg_update_p_kernel<T, TP, K>), dim3(gv), dim3(256), 0, st, n, S, pin, pcur, (const TP*)w.z);
+      SpmvArgs<T, TP> a = spmv_args<T, TP>(A, (const TP*)pcur, Ap);
+      a.order = L0.orderA.p ? dptr<int>(L0.orderA) : nullptr;
+      a.skip = done;
+      a.dotw = nullptr;  // dot with x itself: p'Ap
+      a.partials = w.pc;
+      if (time_it) W.ev.begin(slot, st);
+      spmv_launch_cg<T, K, TP>(a, st);
+    }
+    if (time_it) {
+      W.ev.end(slot, st);
+      ++timed;
+    }
+    auto pap = collapsed(w.pc, plan.spmv_g, w.pcc);
+    hipLaunchKernelGGL((cg_alpha_kernel<K>), dim3(1), dim3(256), 0, st, w.S, pap.first, pap.second);
+    // r -= alpha Ap (+ x += alpha p when the whole solution is wanted), fused with the TP copy of r, the level-0 first
+    // pre-smoothing sweep xa = omega D^-1 r and (when the true residual is monitored) the partials of r'r
+    TP* rpo = MIXED ? w.rp : (TP*)nullptr;
+    if (time_it && plan.use_dia) W.ev2.begin(slot, st);
+    if (plan.fused_rr) {
+      // (the partials of r'r come for free on the recomputing paths; the focal path's post-check reads the last ones instead
+      // of making another pass over r)
+      if constexpr (!MIXED) {
+        RupdRestrictOpts<T> o;
+        if (plan.virtual_r0 && !r0_consumed) o.isrc = pp.pair_src;  // (r holds nothing yet: the kernel synthesises r0)
+        o.idst = pp.need_x ? nullptr : pp.pair_dst;
+        o.icols = pp.pair_cols;
+        o.xsol = x;
+        lattice_rupd_restrict<T, K>(*dia, L0.Ql, S, (const T*)pcur, (const T*)resid.cur(), resid.next(), dptr<T>(H.levels[1].b),
+                                    w.pb, st, o);
+        r0_consumed = true;
+        resid.flip();
+      }
+    } else if (plan.recompute) {
+      dia_residual_update<T, TP, K>(*dia, S, (const TP*)pcur, resid.cur(), rpo, x, w.pb, st);
+    } else {
+      TP* xao = plan.fuse_xa ? dptr<TP>(L0.xa) : (TP*)nullptr;
+      const TP* dinv0 = dptr<TP>(L0.dinv);
+      const TP omega0 = (TP)L0.omega;
+      const bool rr = criterion != CSGPU_CRIT_KRYLOV;
+#define CS_UPD_R(RR, XUP)                                                                                   \
+    hipLaunchKernelGGL((cg_update_r_kernel<T, TP, K, RR, XUP>), dim3(gv), dim3(256), 0, st, n, S, resid.cur(), (const T*)Ap, rpo, \
+                       xao, dinv0, omega0, w.pb, x, (const TP*)pcur)
+      if (rr && pp.need_x) CS_UPD_R(true, true);
+      else if (rr) CS_UPD_R(true, false);
+      else if (pp.need_x) CS_UPD_R(false, true);
+      else CS_UPD_R(false, false);
+#undef CS_UPD_R
+    }
+    if (time_it && plan.use_dia) W.ev2.end(slot, st);
+    T* r = resid.cur();
+    const bool rr_after_mask = (plan.grounded || plan.projected) && criterion != CSGPU_CRIT_KRYLOV;
+    auto masked_rr = [&]() {
+      hipLaunchKernelGGL((dot_kernel<T, K, false>), dim3(gv), dim3(256), 0, st, n, (const T*)r, (const T*)r, w.pb,
+                         (const T*)nullptr, (const T*)nullptr, (double*)nullptr);
+    };
+    if (plan.projected) {  // r <- Pi r: the residual of the projected system (both precisions)
+      poly_project<T, TP, K>(*pp.proj, r, rpo, done, st);
+      if (rr_after_mask) {
+        // ||r||^2 in NODE space = the merged system's (the reference's figure): cell-space partials + one correction row
+        masked_rr();
+        hipLaunchKernelGGL((poly_norm_corr_kernel<K>), dim3(1), dim3(256), 0, st, *pp.proj, w.pb + (size_t)gv * K, done);
+      }
+    }
+    if (plan.grounded) {  // the update put (A p) at the grounded rows into r: back to zero, in both precisions
+      hipLaunchKernelGGL((mask_grounds_kernel<T, TP, K>), dim3(plan.gm), dim3(256), 0, st, pp.gptr, pp.gidx, r, rpo, done);
+      // the partials of r'r the update wrote include alpha (A p) at the Dirichlet rows, which are not equations of the
+      // reduced system (ADVICE r2): when the true residual is monitored, take the norm of the masked r instead
+      if (rr_after_mask) masked_rr();
+    }
+    if (plan.nf > 0)
+      hipLaunchKernelGGL((cg_focal_x_kernel<T, TP, K>), dim3(ceil_div(plan.nf * K, 256)), dim3(256), 0, st, S, fnode, plan.nf,
+                         (const TP*)pcur, xf);
+    fuse.bc_ready = plan.fused_rr;
+    precondition();
+    auto rz = collapsed(w.pa, plan.rz_rows, w.pac);
+    // r'r partials (true-residual criterion): one row per workgroup of whichever kernel updated r
+    const double* prr = w.pb;
+    int nrr = (plan.projected && rr_after_mask) ? gv + 1 : gv;  // (+ the node-space correction row of a polygon handle)
+    if (plan.recompute && criterion != CSGPU_CRIT_KRYLOV && !rr_after_mask) {
+      auto rr = collapsed(w.pb, plan.fused_rr ? plan.rr_fused_rows : plan.spmv_g, w.pcc);
+      prr = rr.first;
+      nrr = rr.second;
+    }
+    hipLaunchKernelGGL((cg_beta_kernel<K>), dim3(1), dim3(256), 0, st, w.S, rz.first, rz.second, prr, nrr, criterion, pp.rtol,
+                       w.atol, 0, ncols_active);
+  }
+
+  // The key of the chunk the loop is about to run: every non-pointer value that reaches a kernel argument of iteration()
+  // comes from the plan, PcgParams or the three pieces of run state read here.
+  PcgGraphKey graph_key() const {
+    PcgGraphKey k;
+    k.K = K;
+    k.ncols_active = ncols_active;
+    k.criterion = criterion;
+    k.nu_pre = pp.nu_pre;
+    k.nu_post = pp.nu_post;
+    k.nu_coarse = pp.nu_coarse;
+    k.iters = plan.chunk;
+    k.rtol = pp.rtol;
+    k.atol = w.atol;
+    k.matrix = (const void*)A.val.p;
+    k.need_x = pp.need_x ? 1 : 0;
+    k.nf = plan.nf;
+    k.parity = parity | (resid.sel << 1);
+    k.fused = plan.fused_rr ? 1 : 0;
+    k.gptr = plan.grounded ? (const void*)pp.gptr : nullptr;
+    k.gidx = plan.grounded ? (const void*)pp.gidx : nullptr;
+    k.gtotal = plan.grounded ? pp.gtotal : 0;
+    k.proj = plan.projected ? (const void*)pp.proj->cells : nullptr;
+    return k;
+  }
+
+  // the captured chunk for the current key (captured now if need be); null = run the launches directly
+  hipGraphExec_t chunk_graph() {
+    const PcgGraphKey gkey = graph_key();
     for (auto& g : W.graphs)
       if (g.first == gkey) return g.second;
     check_launch("pcg before capture");
@@ -1090,19 +1172,14 @@ inline PcgBatchResult pcg_solve(const Csr<T>& A, Hierarchy<TP>& H, PcgWork<T, TP
     hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;
     bool ok = true;
-    const int parity0 = parity, rsel0 = rsel;
+    const int parity0 = parity, rsel0 = resid.snapshot();
     try {
-      for (int c = 0; c < chunk; ++c) iteration(false);
+      for (int c = 0; c < plan.chunk; ++c) iteration(false);
     } catch (...) {
       ok = false;
     }
-    parity = parity0;  // capturing executed nothing: the launch below advances the parity
-    if (fused_rr && rsel != rsel0) {
-      rsel = rsel0;
-      r = rbuf[rsel];
-      rp = (TP*)r;
-      fuse.dotw = rp;
-    }
+    parity = parity0;  // capturing executed nothing: the launch advances the parity
+    resid.restore(rsel0);
     if (hipStreamEndCapture(st, &g) != hipSuccess || !g) ok = false;
     if (ok && hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) != hipSuccess) ok = false;
     if (g) hipGraphDestroy(g);
@@ -1114,162 +1191,163 @@ inline PcgBatchResult pcg_solve(const Csr<T>& A, Hierarchy<TP>& H, PcgWork<T, TP
     if (W.graphs.size() >= 8) W.drop_graphs();
     W.graphs.emplace_back(gkey, ge);
     return ge;
-  };
+  }
 
-  auto run_loop = [&]() {
+  // chunks of `check_every` iterations, one synchronisation each, until every column stopped or itmax
+  void run_loop() {
     while (!host_done && it < pp.itmax) {
-      const int todo = (int)std::min<int64_t>(chunk, (int64_t)pp.itmax - it);
-      gkey.criterion = criterion;
-      gkey.parity = parity | (rsel << 1);
-      gkey.fused = fused_rr ? 1 : 0;
-      hipGraphExec_t ge = (want_graph && it > 0 && todo == chunk) ? chunk_graph() : nullptr;
+      const int todo = (int)std::min<int64_t>(plan.chunk, (int64_t)pp.itmax - it);
+      hipGraphExec_t ge = (plan.want_graph && it > 0 && todo == plan.chunk) ? chunk_graph() : nullptr;
       if (ge) {
         CS_HIP(hipGraphLaunch(ge, st));
-        if (use_dia && (chunk & 1)) parity ^= 1;  // (unreachable: want_graph asks for an even chunk -- which also brings
-        ++graph_launches;                         // the fused update's residual back to the buffer it started in)
+        ++graph_launches;  // (want_graph asks for an even chunk: parity and the fused update's residual end where they started)
       } else {
         for (int c = 0; c < todo; ++c) iteration(true);
       }
       it += todo;
       check_launch("pcg iteration");
-      CS_HIP(hipMemcpyAsync(&host_done, &S->all_done, sizeof(int), hipMemcpyDeviceToHost, st));
+      CS_HIP(hipMemcpyAsync(&host_done, &w.S->all_done, sizeof(int), hipMemcpyDeviceToHost, st));
       CS_HIP(hipStreamSynchronize(st));
     }
-  };
+  }
+
   // the reference's post-check (core.jl:640): ||A x - b|| / ||b||, explicitly when x is carried, otherwise from the
-  // fp64 recurrence residual
-  PcgBatchResult res;
-  res.explicit_relres = need_x;
-  auto post_check = [&]() {
-    if (need_x) {
+  // fp64 recurrence residual; the scalars land in res.s
+  void post_check() {
+    const int gv = plan.gv;
+    const double* num = w.pa;  // relres = sqrt(sum of `nnum` rows of num / sum of `nden` rows of den), den null: ||b|| of start-up
+    const double* den = nullptr;
+    int nnum = gv, nden = 0;
+    DBuf nrm;                      // block-diagonal systems: per-component norms
+    double* worst = nullptr;
+    if (pp.need_x) {
       SpmvArgs<T> a = spmv_args(A, (const T*)x, Ap);
-      a.order = orderA;
+      a.order = H.levels[0].orderA.p ? dptr<int>(H.levels[0].orderA) : nullptr;
       a.b = b;
       spmv_launch<T, K>(a, EPI_RESID, false, st);
-      if (grounded)  // rows of the grounded nodes are not equations of the reduced system
-        hipLaunchKernelGGL((mask_grounds_kernel<T, T, K>), dim3(gm), dim3(256), 0, st, pp.gptr, pp.gidx, Ap, (T*)nullptr,
+      if (plan.grounded)  // rows of the grounded nodes are not equations of the reduced system
+        hipLaunchKernelGGL((mask_grounds_kernel<T, T, K>), dim3(plan.gm), dim3(256), 0, st, pp.gptr, pp.gidx, Ap, (T*)nullptr,
                            (const int*)nullptr);
-      hipLaunchKernelGGL((dot_kernel<T, K, true>), dim3(gv), dim3(256), 0, st, n, (const T*)Ap, (const T*)Ap, pa, b, b, pb);
+      hipLaunchKernelGGL((dot_kernel<T, K, true>), dim3(gv), dim3(256), 0, st, n, (const T*)Ap, (const T*)Ap, w.pa, b, b, w.pb);
+      den = w.pb;
+      nden = gv;
       if (K == 1 && pp.comp_label && pp.ncomp > 1) {
-        DBuf nrm = dalloc<double>((size_t)2 * pp.ncomp + 1);
+        nrm = dalloc<double>((size_t)2 * pp.ncomp + 1);
         CS_HIP(hipMemsetAsync(nrm.p, 0, nrm.bytes, st));
         double* rr = dptr<double>(nrm);
         double* bb = rr + pp.ncomp;
-        hipLaunchKernelGGL((comp_norms_kernel<T>), dim3(grid_for(n)), dim3(256), 0, st, (int)n, pp.comp_label, (const T*)Ap,
-                           b, rr, bb);
+        hipLaunchKernelGGL((comp_norms_kernel<T>), dim3(grid_for(n)), dim3(256), 0, st, (int)n, pp.comp_label, (const T*)Ap, b,
+                           rr, bb);
         hipLaunchKernelGGL(comp_relres_kernel, dim3(1), dim3(256), 0, st, pp.ncomp, (const double*)rr, (const double*)bb,
                            bb + pp.ncomp);
-        hipLaunchKernelGGL((relres_kernel<K>), dim3(1), dim3(256), 0, st, S, (const double*)pa, gv, (const double*)pb, gv);
-        // overwrite column 0's figure with the worst component's
-        CS_HIP(hipMemcpyAsync(&S->relres[0], bb + pp.ncomp, sizeof(double), hipMemcpyDeviceToDevice, st));
-        CS_HIP(hipMemcpyAsync(&res.s, S, sizeof(CgScalars), hipMemcpyDeviceToHost, st));
-        CS_HIP(hipStreamSynchronize(st));
-        return;
+        worst = bb + pp.ncomp;
       }
+    } else if (plan.recompute && it > 0 && !plan.grounded && !plan.projected) {
+      // fp64 recurrence residual against ||b|| recorded at start-up:
+      // ||r||^2 partials of the last residual update that ran (surplus launches exit before writing)
+      auto rr = collapsed(w.pb, plan.fused_rr ? plan.rr_fused_rows : plan.spmv_g, w.pcc);
+      num = rr.first;
+      nnum = rr.second;
     } else {
-      // fp64 recurrence residual against ||b|| recorded at start-up
-      if (recompute && it > 0 && !grounded && !projected) {
-        // ||r||^2 partials of the last residual update that ran (surplus launches exit before writing)
-        auto rr = collapsed(pb, fused_rr ? rr_fused_rows : spmv_g, pcc);
-        hipLaunchKernelGGL((relres_kernel<K>), dim3(1), dim3(256), 0, st, S, rr.first, rr.second, (const double*)nullptr, 0);
-      } else {
-        hipLaunchKernelGGL((dot_kernel<T, K, false>), dim3(gv), dim3(256), 0, st, n, (const T*)r, (const T*)r, pa,
-                           (const T*)nullptr, (const T*)nullptr, (double*)nullptr);
-        int rows = gv;
-        if (projected) {
-          // polygon handle: the figure of the MERGED system, ||b_m - A_m y|| / ||b_m|| (src/core.jl:640-641) -- r is
-          // polygon-wise constant, its chunk sums are taken again (the last projection was z's), the correction row follows
-          hipLaunchKernelGGL((poly_chunk_sum_kernel<T, K>), dim3(pp.proj->nchunks), dim3(256), 0, st, *pp.proj, (const T*)r,
-                             (const int*)nullptr);
-          hipLaunchKernelGGL((poly_norm_corr_kernel<K>), dim3(1), dim3(256), 0, st, *pp.proj, pa + (size_t)gv * K,
-                             (const int*)nullptr);
-          rows = gv + 1;
-        }
-        hipLaunchKernelGGL((relres_kernel<K>), dim3(1), dim3(256), 0, st, S, (const double*)pa, rows, (const double*)nullptr,
-                           0);
+      const T* r = resid.cur();
+      hipLaunchKernelGGL((dot_kernel<T, K, false>), dim3(gv), dim3(256), 0, st, n, r, r, w.pa, (const T*)nullptr,
+                         (const T*)nullptr, (double*)nullptr);
+      if (plan.projected) {
+        // polygon handle: the figure of the MERGED system, ||b_m - A_m y|| / ||b_m|| (src/core.jl:640-641) -- r is
+        // polygon-wise constant, its chunk sums are taken again (the last projection was z's), the correction row follows
+        hipLaunchKernelGGL((poly_chunk_sum_kernel<T, K>), dim3(pp.proj->nchunks), dim3(256), 0, st, *pp.proj, r,
+                           (const int*)nullptr);
+        hipLaunchKernelGGL((poly_norm_corr_kernel<K>), dim3(1), dim3(256), 0, st, *pp.proj, w.pa + (size_t)gv * K,
+                           (const int*)nullptr);
+        nnum = gv + 1;
       }
-      CS_HIP(hipMemcpyAsync(&res.s, S, sizeof(CgScalars), hipMemcpyDeviceToHost, st));
-      CS_HIP(hipStreamSynchronize(st));
-      return;
     }
-    hipLaunchKernelGGL((relres_kernel<K>), dim3(1), dim3(256), 0, st, S, (const double*)pa, gv, (const double*)pb, gv);
-    CS_HIP(hipMemcpyAsync(&res.s, S, sizeof(CgScalars), hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL((relres_kernel<K>), dim3(1), dim3(256), 0, st, w.S, num, nnum, den, nden);
+    if (worst)  // overwrite column 0's figure with the worst component's
+      CS_HIP(hipMemcpyAsync(&w.S->relres[0], worst, sizeof(double), hipMemcpyDeviceToDevice, st));
+    CS_HIP(hipMemcpyAsync(&res.s, w.S, sizeof(CgScalars), hipMemcpyDeviceToHost, st));
     CS_HIP(hipStreamSynchronize(st));
-  };
-  run_loop();
-  post_check();
-  // Polishing. Krylov.jl's rule stops on the PRECONDITIONED residual norm; on nearly singular grounded systems (one
-  // weak ground in a large component) that norm can be 100x more optimistic than ||Ax-b||/||b||, and the reference's
-  // own 1e-4 check (core.jl:640) is then decided by how the preconditioner happens to weight the near-null space.
-  // A column that stopped "converged" but would fail that check is re-opened and iterated on the true residual
-  // (CG restarts from x with p = z: state is consistent, see cg_reopen_kernel) until ||r||/||b|| <= 2.5e-5. Columns
-  // that pass -- every case in which the reference's rule is adequate -- are untouched, bit for bit.
-  {
+  }
+
+  // Polishing. Krylov.jl's rule stops on the PRECONDITIONED residual norm; on nearly singular grounded systems (one weak
+  // ground in a large component) that norm can be 100x more optimistic than ||Ax-b||/||b||, and the reference's own 1e-4
+  // check (core.jl:640) is then decided by how the preconditioner happens to weight the near-null space. A column that
+  // stopped "converged" but would fail that check is re-opened and iterated on the true residual (CG restarts from x with
+  // p = z: state is consistent, see cg_reopen_kernel) until ||r||/||b|| <= 2.5e-5. Columns that pass -- every case in which
+  // the reference's rule is adequate -- are untouched, bit for bit.
+  void polish() {
     bool reopen = false;
     for (int c = 0; c < ncols_active && c < kMaxK; ++c)
       if (res.s.done[c] == 1 && !(res.s.relres[c] < 1e-4)) reopen = true;
-    if (reopen && it < pp.itmax) {
-      if (fused_rr) {
-        // Launches enqueued after the last column stopped returned without writing (device flag), yet each re-pointed r on
-        // the host: the residual is in the buffer the last REAL update wrote -- update number max_c iters[c] of this solve
-        // (buffer 0 holds r_0). The polishing phase then runs the two-pass update in place.
-        int real = 0;
-        for (int c = 0; c < ncols_active && c < kMaxK; ++c) real = std::max(real, res.s.iters[c]);
-        rsel = real & 1;
-        r = rbuf[rsel];
-        rp = (TP*)r;
-        fuse.dotw = rp;
-        fused_rr = false;
-      }
-      criterion = CSGPU_CRIT_TRUE_RESIDUAL;
-      hipLaunchKernelGGL((cg_reopen_kernel<K>), dim3(1), dim3(64), 0, st, S, 1e-4, 2.5e-5, ncols_active);
-      host_done = 0;
-      run_loop();
-      post_check();
-      res.polished = 1;
+    if (!reopen || it >= pp.itmax) return;
+    if (plan.fused_rr) {  // the polishing phase runs the two-pass update in place, from the buffer that holds the residual
+      resid.rewind_to_update(real_updates());
+      plan.fused_rr = false;
     }
+    criterion = CSGPU_CRIT_TRUE_RESIDUAL;
+    hipLaunchKernelGGL((cg_reopen_kernel<K>), dim3(1), dim3(64), 0, st, w.S, 1e-4, 2.5e-5, ncols_active);
+    host_done = 0;
+    run_loop();
+    post_check();
+    res.polished = 1;
   }
-  CS_HIP(hipEventRecord(e1, st));
+
+  // launch times and algorithmic byte counts of the result
+  void summary() {
+    // launches enqueued after every column had converged return immediately: leave them out of the average
+    // (on the lattice path the timed launches are those of iterations 1, 2, ...: the first one is shorter, see first_product)
+    const int counted = std::min(timed, std::max(real_updates() - (plan.use_dia ? 1 : 0), 0));
+    res.spmv_ms = W.ev.sum_ms(counted);
+    res.spmv_calls = counted;
+    if (plan.use_dia) {
+      // algorithmic bytes of one residual-update launch: the lattice rows, p, r read and written (+ its copy in the
+      // preconditioner's precision); fused with the restriction: + the nine values of Q per row and the coarse right-hand side
+      res.resid_ms = W.ev2.sum_ms(counted);
+      res.resid_calls = counted;
+      res.resid_bytes = n * 5 * (int64_t)sizeof(T) + n * K * ((int64_t)sizeof(TP) + 2 * (int64_t)sizeof(T) + (MIXED ? (int64_t)sizeof(TP) : 0));
+      if (res.resid_fused && H.levels.size() > 1)
+        res.resid_bytes += n * 9 * (int64_t)sizeof(T) + (int64_t)H.levels[1].A.nrows * K * (int64_t)sizeof(T);
+      // (the fused pass that carries the solution: x read and written; the two-pass figure has never counted x)
+      if (res.resid_fused && pp.need_x) res.resid_bytes += 2 * n * K * (int64_t)sizeof(T);
+      if (!plan.recompute) res.resid_bytes = 0;  // (the generic update kernel: not this formula)
+    }
+    res.graph_launches = graph_launches;
+    if (plan.use_dia)
+      res.spmv_bytes = n * 5 * (int64_t)sizeof(T) + n * K * (3 * (int64_t)sizeof(TP) + (plan.recompute ? 0 : (int64_t)sizeof(T)));
+    else
+      res.spmv_bytes = A.nnz * (int64_t)(sizeof(T) + 4) + (n + 1) * 4 + n * K * (int64_t)(sizeof(TP) + sizeof(T));
+  }
+};
+
+// Solve A X = B for the K interleaved columns held in W.b. With pp.need_x the solution is left in W.x; otherwise only
+// the entries at W.fnode are accumulated (W.xf) and W.x is not touched (not even allocated).
+// A is the matrix CG sees (precision T); H is the hierarchy (precision TP) whose level 0 has A's sparsity pattern.
+// `dia`: optional symmetric-diagonal (lattice) form of A (stencil.h); when given, the product A p is evaluated from it
+// with the search-direction update p = z + beta p fused in, and A's CSR form is only used by the explicit post-check.
+template <class T, class TP, int K>
+inline PcgBatchResult pcg_solve(const Csr<T>& A, Hierarchy<TP>& H, PcgWork<T, TP>& W, const PcgParams& pp,
+                                int ncols_active, hipStream_t st, const Dia<T>* dia = nullptr) {
+  const int64_t n = A.nrows;
+  ensure_level_work(H, K);
+  if (pp.need_x) W.need_vec(W.x);
+  const PcgPtrs<T, TP> w = pcg_ptrs<T, TP>(W, pp, dia && dia->n == n);
+  LaunchTimer span;
+  span.begin(0, st);
+  PcgRun<T, TP, K> q{A, H, W, pp, dia, ncols_active, st, n, w, pcg_plan<T, TP, K>(A, H, W, pp, dia)};
+  q.fuse.b_has_tail = q.plan.two_product;
+  q.fuse.partials = w.pa;
+  q.res.explicit_relres = pp.need_x;
+  q.res.resid_fused = q.plan.fused_rr ? 1 : 0;  // (before any polishing)
+  q.setup();
+  q.run_loop();
+  q.post_check();
+  q.polish();
+  span.end(0, st);
   CS_HIP(hipStreamSynchronize(st));
   check_launch("pcg finish");
-  float ms = 0;
-  CS_HIP(hipEventElapsedTime(&ms, e0, e1));
-  res.device_ms = ms;
-  // launches enqueued after every column had converged return immediately (device flag): leave them out of the average
-  int real_its = 0;
-  for (int c = 0; c < ncols_active && c < kMaxK; ++c) real_its = std::max(real_its, res.s.iters[c]);
-  // (on the lattice path the timed launches are those of iterations 1, 2, ...: the first one is shorter, see `iteration`)
-  const int counted = std::min(timed, std::max(real_its - (use_dia ? 1 : 0), 0));
-  for (int t = 0; t < counted; ++t) {
-    float m2 = 0;
-    CS_HIP(hipEventElapsedTime(&m2, W.ev[2 * t], W.ev[2 * t + 1]));
-    res.spmv_ms += m2;
-    if (use_dia) {
-      CS_HIP(hipEventElapsedTime(&m2, W.ev2[2 * t], W.ev2[2 * t + 1]));
-      res.resid_ms += m2;
-    }
-  }
-  res.spmv_calls = counted;
-  if (use_dia) {
-    // algorithmic bytes of one residual-update launch: the lattice rows, p, r read and written (+ its copy in the
-    // preconditioner's precision); fused with the restriction: + the nine values of Q per row and the coarse right-hand side
-    res.resid_calls = counted;
-    res.resid_fused = rbuf[1] ? 1 : 0;  // (the second residual buffer exists only on the fused path)
-    res.resid_bytes = n * 5 * (int64_t)sizeof(T) + n * K * ((int64_t)sizeof(TP) + 2 * (int64_t)sizeof(T) + (MIXED ? (int64_t)sizeof(TP) : 0));
-    if (res.resid_fused && H.levels.size() > 1)
-      res.resid_bytes += n * 9 * (int64_t)sizeof(T) + (int64_t)H.levels[1].A.nrows * K * (int64_t)sizeof(T);
-    // (the fused pass that carries the solution: x read and written; the two-pass figure has never counted x)
-    if (res.resid_fused && need_x) res.resid_bytes += 2 * n * K * (int64_t)sizeof(T);
-    if (!recompute) res.resid_bytes = 0;  // (the generic update kernel: not this formula)
-  }
-  res.graph_launches = graph_launches;
-  if (use_dia)
-    res.spmv_bytes = n * 5 * (int64_t)sizeof(T) + n * K * (3 * (int64_t)sizeof(TP) + (recompute ? 0 : (int64_t)sizeof(T)));
-  else
-    res.spmv_bytes = A.nnz * (int64_t)(sizeof(T) + 4) + (n + 1) * 4 + n * K * (int64_t)(sizeof(TP) + sizeof(T));
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  return res;
+  q.res.device_ms = span.sum_ms(1);
+  q.summary();
+  return q.res;
 }
 
 // ---- streaming pair solves ("continuous batching") ---------------------------------------------------------------------
@@ -1334,44 +1412,25 @@ inline PcgStreamResult pcg_stream_pairs(Hierarchy<TP>& H, PcgWork<T, TP>& W, con
   res.status.assign((size_t)npairs, 1);
   res.relres.assign((size_t)npairs, 0.0);
   ensure_level_work(H, K);
-  if (W.p2.bytes < (size_t)n * K * sizeof(TP)) {
-    W.drop_graphs();
-    W.p2.alloc((size_t)n * K * sizeof(TP));
-  }
+  const PcgPtrs<T, TP> w = pcg_ptrs<T, TP>(W, pp, true);
   W.set_focal(focal, st);
   W.have_x = false;
   const int nf = W.nf;
-  T* r = dptr<T>(W.r);
-  TP* pbuf[2] = {dptr<TP>(W.p), dptr<TP>(W.p2)};
-  TP* z = dptr<TP>(W.z);
-  TP* rp = MIXED ? dptr<TP>(W.rp) : (TP*)r;
-  CgScalars* S = dptr<CgScalars>(W.scalars);
-  double* pa = dptr<double>(W.part_a);
-  double* pb = dptr<double>(W.part_b);
-  double* pc = dptr<double>(W.part_c);
-  double* pac = dptr<double>(W.part_ca);
-  double* pcc = dptr<double>(W.part_cc);
+  TP* const* pbuf = w.pbuf;
+  TP* z = w.z;
+  CgScalars* S = w.S;
   if (W.part_cb.bytes < (size_t)kCollapsedParts * kMaxK * sizeof(double)) W.part_cb.alloc((size_t)kCollapsedParts * kMaxK * sizeof(double));
   double* pbc = dptr<double>(W.part_cb);
   T* xf = dptr<T>(W.xf);
   const int* fnode = dptr<int>(W.fnode);
-  const double atol = pp.atol < 0 ? std::sqrt((double)std::numeric_limits<T>::epsilon()) : pp.atol;
   const int spmv_g = dia_grid<T, TP, K>(dia);
   const int spmv_gp = dia_grid<TP, TP, K>(L0.Sdia);
-  const int collapse_min = knobs().collapse_min >= 0 ? (int)std::max<int64_t>(1, knobs().collapse_min) : 4 * kCollapsedParts;
-  auto collapsed = [&](double* from, int nparts, double* to) -> std::pair<const double*, int> {
-    if (nparts <= collapse_min) return {from, nparts};
-    hipLaunchKernelGGL((collapse_partials_kernel<K>), dim3(ceil_div(kCollapsedParts * K, 256)), dim3(256), 0, st,
-                       (const double*)from, nparts, to);
-    return {to, kCollapsedParts};
-  };
-  hipEvent_t e0, e1;
-  CS_HIP(hipEventCreate(&e0));
-  CS_HIP(hipEventCreate(&e1));
-  CS_HIP(hipEventRecord(e0, st));
+  auto collapsed = [&](double* from, int nparts, double* to) { return collapse_partials<K>(from, nparts, to, w.collapse_min, st); };
+  LaunchTimer span;
+  span.begin(0, st);
   // every vector finite before the first pass (a slot's first iteration multiplies stale values by zero)
-  CS_HIP(hipMemsetAsync(r, 0, (size_t)n * K * sizeof(T), st));
-  if (MIXED) CS_HIP(hipMemsetAsync(rp, 0, (size_t)n * K * sizeof(TP), st));
+  CS_HIP(hipMemsetAsync(w.r, 0, (size_t)n * K * sizeof(T), st));
+  if (MIXED) CS_HIP(hipMemsetAsync(w.rp, 0, (size_t)n * K * sizeof(TP), st));
   CS_HIP(hipMemsetAsync(z, 0, (size_t)n * K * sizeof(TP), st));
   CS_HIP(hipMemsetAsync(pbuf[0], 0, (size_t)n * K * sizeof(TP), st));
   CS_HIP(hipMemsetAsync(pbuf[1], 0, (size_t)n * K * sizeof(TP), st));
@@ -1413,34 +1472,19 @@ inline PcgStreamResult pcg_stream_pairs(Hierarchy<TP>& H, PcgWork<T, TP>& W, con
   CS_HIP(hipMemcpyAsync(S, &hs, sizeof(CgScalars), hipMemcpyHostToDevice, st));
   VcycleFuse<TP> fuse;
   fuse.b_has_tail = true;
-  fuse.dotw = rp;
-  fuse.partials = pa;
-  Enrich& EN = H.enr;  // (enrich.h; as in pcg_solve)
+  fuse.partials = w.pa;
   // (the stream only runs on the lattice two-product path of a handle without polygons -- checked above and by the caller)
-  const bool enrich = enrich_applicable<TP>(EN, n, two_product, pp.proj != nullptr);
-  if (enrich && (EN.work_k != K || EN.work_bytes != (int)sizeof(TP))) {
-    W.drop_graphs();
-    enrich_ensure_work<TP, K>(EN);
-  }
+  const bool enrich = enrich_applicable<TP>(H.enr, n, two_product, pp.proj != nullptr);
+  if (enrich) enrich_prepare<TP, K>(H.enr, W);
   const int rz_rows = spmv_gp + (enrich ? kEnrichParts : 0);
-  // fused residual update + restriction (see pcg_solve): the residual ping-pongs between W.r and W.r2
-  bool fused_rr = false;
-  T* rbuf[2] = {r, nullptr};
-  int rsel = 0, rr_rows = spmv_g;
-  if constexpr (!MIXED && lattice_rupd_restrict_fits<T, K>()) {
-    fused_rr = fused_restrict_wanted<T>() && (!enrich || EN.ntouch > 0);
-    if (fused_rr) {
-      const size_t want = ((size_t)n + (size_t)W.tail) * K * sizeof(T);
-      if (W.r2.bytes < want) {
-        W.drop_graphs();
-        W.r2.alloc(want);
-      }
-      rbuf[1] = dptr<T>(W.r2);
-      int a_, b_, c_;
-      rr_rows = lattice_rupd_restrict_grid<T, K>(L0.Ql, a_, b_, c_);
-      ++H.fused_restrict_solves;
-    }
-  }
+  // the stream's constants in the batch solve's predicate: A p recomputed, two-product lattice level, no x, no masks
+  // (a second residual buffer an earlier batch solve left stays where it is)
+  const int rr_fused_rows = acquire_fused_residual<T, TP, K>(H, W, pp, n, enrich, true, true, false, false, false);
+  const bool fused_rr = rr_fused_rows > 0;
+  const int rr_rows = fused_rr ? rr_fused_rows : spmv_g;
+  ResidualPingPong<T, TP> rr{{w.r, fused_rr ? dptr<T>(W.r2) : nullptr}, w.rp};
+  fuse.bc_ready = fused_rr;  // (every cycle of the loop follows a fused update)
+  const RupdRestrictOpts<T> restarts{S->ctl.restart, S->ctl.src, S->ctl.dst};
   const int max_timed = knobs().timed_launches;
   int timed = 0;
   int parity = 0;
@@ -1449,56 +1493,32 @@ inline PcgStreamResult pcg_stream_pairs(Hierarchy<TP>& H, PcgWork<T, TP>& W, con
     const TP* pin = pbuf[parity];
     TP* pcur = pbuf[parity ^ 1];
     const bool time_it = timed < max_timed;
-    if (time_it) {
-      if ((int)W.ev.size() < 2 * (timed + 1)) {
-        hipEvent_t ea, eb;
-        CS_HIP(hipEventCreate(&ea));
-        CS_HIP(hipEventCreate(&eb));
-        W.ev.push_back(ea);
-        W.ev.push_back(eb);
-      }
-      CS_HIP(hipEventRecord(W.ev[2 * timed], st));
-    }
-    dia_cg_product<T, TP, K>(dia, (const CgScalars*)S, (const TP*)z, pin, pcur, (T*)nullptr, pc, st);
-    if (time_it) {
-      CS_HIP(hipEventRecord(W.ev[2 * timed + 1], st));
-      ++timed;
-    }
+    if (time_it) W.ev.begin(timed, st);
+    dia_cg_product<T, TP, K>(dia, (const CgScalars*)S, (const TP*)z, pin, pcur, (T*)nullptr, w.pc, st);
+    if (time_it) W.ev.end(timed++, st);
     parity ^= 1;
-    {
-      auto pap = collapsed(pc, spmv_g, pcc);
-      hipLaunchKernelGGL((cg_alpha_kernel<K>), dim3(1), dim3(256), 0, st, S, pap.first, pap.second);
-    }
+    auto pap = collapsed(w.pc, spmv_g, w.pcc);
+    hipLaunchKernelGGL((cg_alpha_kernel<K>), dim3(1), dim3(256), 0, st, S, pap.first, pap.second);
     if (fused_rr) {
       if constexpr (!MIXED) {
-        T* rnew = rbuf[rsel ^ 1];
-        lattice_rupd_restrict<T, K>(dia, L0.Ql, (const CgScalars*)S, (const T*)pcur, (const T*)r, rnew, dptr<T>(H.levels[1].b),
-                                    pb, st, (const int*)S->ctl.restart, (const int*)S->ctl.src, (const int*)S->ctl.dst);
-        rsel ^= 1;
-        r = rnew;
-        rp = (TP*)rnew;
-        fuse.dotw = rp;
-        fuse.bc_ready = true;
+        lattice_rupd_restrict<T, K>(dia, L0.Ql, (const CgScalars*)S, (const T*)pcur, (const T*)rr.cur(), rr.next(),
+                                    dptr<T>(H.levels[1].b), w.pb, st, restarts);
+        rr.flip();
       }
     } else {
-      dia_residual_update<T, TP, K>(dia, (const CgScalars*)S, (const TP*)pcur, r, MIXED ? rp : (TP*)nullptr, (T*)nullptr, pb,
-                                    st, (const int*)S->ctl.restart);
+      dia_residual_update<T, TP, K>(dia, (const CgScalars*)S, (const TP*)pcur, rr.cur(), MIXED ? w.rp : (TP*)nullptr, (T*)nullptr,
+                                    w.pb, st, (const int*)S->ctl.restart);
     }
     if (nf > 0)
       hipLaunchKernelGGL((cg_focal_x_kernel<T, TP, K>), dim3(ceil_div(nf * K, 256)), dim3(256), 0, st, (const CgScalars*)S,
                          fnode, nf, (const TP*)pcur, xf);
-    hipLaunchKernelGGL((stream_restart_kernel<T, TP, K>), dim3(1), dim3(256), 0, st, (const CgScalars*)S, r,
-                       MIXED ? rp : (TP*)nullptr, nf, xf);
-    if (enrich) enrich_pre<TP, K, !MIXED>(EN, rp, (const int*)nullptr, st);
-    if (enrich && fuse.bc_ready) enrich_coarse_fix<TP, K>(EN, dptr<TP>(H.levels[1].b), (const int*)nullptr, st);
-    vcycle<TP, K>(H, 0, rp, z, pp.nu_pre, pp.nu_post, pp.nu_coarse, st, &fuse);
-    if (enrich) enrich_post<TP, K, !MIXED>(EN, rp, z, pa + (size_t)spmv_gp * K, (const int*)nullptr, st);
-    {
-      auto rz = collapsed(pa, rz_rows, pac);
-      auto rr = collapsed(pb, rr_rows, pbc);
-      hipLaunchKernelGGL((cg_stream_beta_kernel<K>), dim3(1), dim3(256), 0, st, S, rz.first, rz.second, rr.first, rr.second,
-                         pp.criterion, pp.rtol, atol, pp.itmax);
-    }
+    hipLaunchKernelGGL((stream_restart_kernel<T, TP, K>), dim3(1), dim3(256), 0, st, (const CgScalars*)S, rr.cur(),
+                       MIXED ? w.rp : (TP*)nullptr, nf, xf);
+    apply_preconditioner<T, TP, K>(H, pp, fuse, rr, z, enrich, spmv_gp, st);
+    auto rz = collapsed(w.pa, rz_rows, w.pac);
+    auto rrp = collapsed(w.pb, rr_rows, pbc);
+    hipLaunchKernelGGL((cg_stream_beta_kernel<K>), dim3(1), dim3(256), 0, st, S, rz.first, rz.second, rrp.first, rrp.second,
+                       pp.criterion, pp.rtol, w.atol, pp.itmax);
     check_launch("pcg stream iteration");
     ++res.slots;
     CS_HIP(hipMemcpyAsync(&hs, S, sizeof(CgScalars), hipMemcpyDeviceToHost, st));
@@ -1530,21 +1550,13 @@ inline PcgStreamResult pcg_stream_pairs(Hierarchy<TP>& H, PcgWork<T, TP>& W, con
     CS_HIP(hipMemcpyAsync(&S->ctl, &hs.ctl, sizeof(hs.ctl), hipMemcpyHostToDevice, st));
     CS_HIP(hipMemcpyAsync(&S->all_done, &hs.all_done, sizeof(int), hipMemcpyHostToDevice, st));
   }
-  CS_HIP(hipEventRecord(e1, st));
+  span.end(0, st);
   CS_HIP(hipStreamSynchronize(st));
   check_launch("pcg stream finish");
-  float ms = 0;
-  CS_HIP(hipEventElapsedTime(&ms, e0, e1));
-  res.device_ms = ms;
-  for (int t = 0; t < timed; ++t) {
-    float m2 = 0;
-    CS_HIP(hipEventElapsedTime(&m2, W.ev[2 * t], W.ev[2 * t + 1]));
-    res.spmv_ms += m2;
-  }
+  res.device_ms = span.sum_ms(1);
+  res.spmv_ms = W.ev.sum_ms(timed);
   res.spmv_calls = timed;
   res.spmv_bytes = n * 5 * (int64_t)sizeof(T) + n * K * 3 * (int64_t)sizeof(TP);
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
   return res;
 }
 
