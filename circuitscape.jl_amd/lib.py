@@ -392,7 +392,7 @@ class Handle:
         return ms.value
 
     def spmv(self, x):
-        """y = A x for x of shape (n,) or (n, k) with k in {1,2,4,8,16} (host arrays; test helper)."""
+        """y = A x for x of shape (n,) or (n, k) with k in {1,2,4,8,16,32} (host arrays; test helper)."""
         x = np.asarray(x, dtype=self.dtype)
         k = 1 if x.ndim == 1 else x.shape[1]
         xi = np.ascontiguousarray(x.reshape(x.shape[0], k))  # C order == interleaved [n][k]
