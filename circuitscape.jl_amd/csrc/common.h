@@ -95,6 +95,9 @@ struct Knobs {
   int fused_seg = 64;             // coarse columns per tile of that pass (restrict_seg, when given, sets both)
   int fused_level1 = 0;           // lattice V(2,2) levels: 1 = x = S b and b_c = Q2' b in one pass over b, 2 = also out = x + S (b - A x) + Q2 x_c in one
                                   // chained pass, -1 = four passes, 0 = per precision (pcg.h)
+  int lattice_maps = 0;           // voltage / current maps and the explicit post-check of pair solves from the lattice form
+                                  // (lattice_currents.h): 1 = wherever it applies, -1 = never, 0 = only where the handle cannot
+                                  // hold a CSR form (2^31 stored entries)
   bool sparse_init = true;        // fused path, pair solves: r0 = e_dst - e_src is never stored (PcgParams::pair_src, pcg.h)
   int64_t collapse_min = -1;      // < 0: the default rule of pcg.h
   bool longrow = true, narrow_tile = false;

@@ -7,6 +7,7 @@
 #include <thread>
 
 #include "currents.h"
+#include "lattice_currents.h"
 #include "pairs.h"
 #include "pcg.h"
 #include "raster.h"
@@ -80,6 +81,7 @@ inline Knobs knobs_from_opts(const csgpu_opts& o) {
   k.fused_restrict = o.fused_restrict > 0 ? 1 : (o.fused_restrict < 0 ? -1 : 0);
   if (o.sparse_init != 0) k.sparse_init = o.sparse_init > 0;
   k.fused_level1 = o.fused_level1 > 0 ? std::min(o.fused_level1, 2) : (o.fused_level1 < 0 ? -1 : 0);
+  k.lattice_maps = o.lattice_maps > 0 ? 1 : (o.lattice_maps < 0 ? -1 : 0);
   k.longrow = flag(o.longrow, true);
   k.narrow_tile = o.narrow_tile > 0;
   if (o.spmv_grid_cap != 0) k.spmv_grid_cap = std::max(o.spmv_grid_cap, 0);
@@ -143,6 +145,7 @@ inline Knobs knobs_from_opts(const csgpu_opts& o) {
   num("FUSED_RESTRICT", [&](double v) { k.fused_restrict = v > 0 ? 1 : -1; });
   num("SPARSE_INIT", [&](double v) { k.sparse_init = v > 0; });
   num("FUSED_LEVEL1", [&](double v) { k.fused_level1 = v > 0 ? (v >= 2 ? 2 : 1) : -1; });
+  num("LATTICE_MAPS", [&](double v) { k.lattice_maps = v > 0 ? 1 : (v < 0 ? -1 : 0); });
   num("COLLAPSE_MIN", [&](double v) { k.collapse_min = (int64_t)v; });
   if (on("NO_LONGROW")) k.longrow = false;
   if (on("NARROW_TILE")) k.narrow_tile = true;
@@ -832,6 +835,15 @@ struct Solver : ISolver {
     } else {
       return H.levels[0].A;
     }
+  }
+  // Pair solves that hand back voltages, node currents, cumulative / maximum maps or run the explicit residual check: served
+  // from the lattice form (lattice_currents.h, PcgParams::lattice_check) instead of the CSR form? Raster numbering only (the
+  // device rows are monotone in the caller's nodes, so a branch's orientation is that of the device ids); branch currents are
+  // indexed by the stored entries of a CSR matrix and stay there.
+  bool lattice_maps_path(bool want_branch) const {
+    if (!dia_ptr() || poly_proj || reordered || want_branch || kn.lattice_maps < 0) return false;
+    if (kn.lattice_maps > 0) return true;
+    return !csr_ready && nnz >= ((int64_t)1 << 31);  // default: only where ensure_csr() would refuse
   }
   // CSR form of the fine-level matrix, built from the lattice form when the handle was set up without one
   void ensure_csr() {
@@ -1712,9 +1724,10 @@ struct Solver : ISolver {
 
   template <int K>
   PcgBatchResult run_batch(int ncols, bool need_x, const double* bb_host = nullptr, const int* pair_src = nullptr,
-                           const int* pair_dst = nullptr) {
+                           const int* pair_dst = nullptr, bool lattice_check = false) {
     PcgParams pp = pcg_params(K);
     pp.need_x = need_x;
+    pp.lattice_check = lattice_check;  // (solve_pairs on the lattice-maps path: the post-check reads no CSR array)
     pp.rhs_in_r = !need_x;  // (only solve_pairs runs without the whole solution; it hands the pairs over instead of b:
     pp.rp_ready = false;    //  pcg_solve writes -- or synthesises -- the +-1 entries of r0, and ||b||^2 = 2 is known)
     pp.bb_host = need_x ? nullptr : bb_host;
@@ -1726,14 +1739,14 @@ struct Solver : ISolver {
     return pcg_solve<T, TP, K>(cg_matrix(), H, W, pp, ncols, st, dia_ptr());
   }
   PcgBatchResult run_batch_k(int K, int ncols, bool need_x = true, const double* bb_host = nullptr,
-                             const int* pair_src = nullptr, const int* pair_dst = nullptr) {
+                             const int* pair_src = nullptr, const int* pair_dst = nullptr, bool lattice_check = false) {
     switch (K) {
-      case 1: return run_batch<1>(ncols, need_x, bb_host, pair_src, pair_dst);
-      case 2: return run_batch<2>(ncols, need_x, bb_host, pair_src, pair_dst);
-      case 4: return run_batch<4>(ncols, need_x, bb_host, pair_src, pair_dst);
-      case 8: return run_batch<8>(ncols, need_x, bb_host, pair_src, pair_dst);
-      case 32: return run_batch<32>(ncols, need_x, bb_host, pair_src, pair_dst);
-      default: return run_batch<16>(ncols, need_x, bb_host, pair_src, pair_dst);
+      case 1: return run_batch<1>(ncols, need_x, bb_host, pair_src, pair_dst, lattice_check);
+      case 2: return run_batch<2>(ncols, need_x, bb_host, pair_src, pair_dst, lattice_check);
+      case 4: return run_batch<4>(ncols, need_x, bb_host, pair_src, pair_dst, lattice_check);
+      case 8: return run_batch<8>(ncols, need_x, bb_host, pair_src, pair_dst, lattice_check);
+      case 32: return run_batch<32>(ncols, need_x, bb_host, pair_src, pair_dst, lattice_check);
+      default: return run_batch<16>(ncols, need_x, bb_host, pair_src, pair_dst, lattice_check);
     }
   }
 
@@ -1890,7 +1903,12 @@ struct Solver : ISolver {
     // resistance-only calls consume x at the pairs' nodes and the gathered focal nodes only (core.jl:231-232,
     // 685-703): accumulate just those entries instead of carrying the n x K solution through every iteration
     const bool need_x = volt_out || want_curr || opts.explicit_check > 0;
-    if (need_x) ensure_csr();  // (the explicit residual check and the current kernels walk the CSR form)
+    // The explicit residual check and the current kernels of currents.h walk the CSR form; on the lattice-maps path
+    // (csgpu_opts.lattice_maps) the post-check is dia_apply's and the currents come from lattice_currents.h: no CSR array is read
+    // and none is built.
+    const bool lattice_maps = need_x && lattice_maps_path(branch_out != nullptr);
+    if (need_x && !lattice_maps) ensure_csr();
+    if (stats) stats->lattice_maps = lattice_maps ? 1 : 0;
     std::vector<int> focal;
     if (!need_x) focal.resize((size_t)ngather + 2 * Kmax);
     DBuf dcurr, dcum, dmax, dweight, dbpart, dbmax, dbranch, dbranch2;
@@ -1901,9 +1919,11 @@ struct Solver : ISolver {
       dbranch2.alloc((size_t)std::max<int64_t>(nnz, 1) * Kmax * sizeof(T));
     }
     if (want_curr) {
-      dcurr.alloc((size_t)n * Kmax * sizeof(T));
+      // (lattice path: the currents are stored only when the caller wants them -- the cumulative / maximum maps are accumulated
+      // inside the kernel -- and the partial maxima are sized per batch from that launch's grid)
+      if (!lattice_maps || curr_out) dcurr.alloc((size_t)n * Kmax * sizeof(T));
       dweight.alloc((size_t)Kmax * sizeof(int));
-      dbpart.alloc((size_t)kMaxGrid * Kmax * 2 * sizeof(double));
+      if (!lattice_maps) dbpart.alloc((size_t)kMaxGrid * Kmax * 2 * sizeof(double));
       dbmax.alloc((size_t)Kmax * 2 * sizeof(double));
       if (cum_inout) {
         dcum.alloc((size_t)n * sizeof(T));
@@ -1952,7 +1972,8 @@ struct Solver : ISolver {
         }
         W.set_focal(focal, st);
       }
-      PcgBatchResult r = run_batch_k(K, ncols, need_x, bb, dptr<int>(dsrc), dptr<int>(ddst));
+      PcgBatchResult r = run_batch_k(K, ncols, need_x, bb, dptr<int>(dsrc), dptr<int>(ddst), lattice_maps);
+      CS_REQUIRE(!lattice_maps || r.lattice_check == 1, CSGPU_INTERNAL, "lattice-maps call whose post-check left the lattice form");
       accumulate(stats, r, ncols);
       if (stream_eligible && ncols == K) {
         // spread of this batch's iteration counts: stream the rest when (mean + 1) slots per pair beat (max + 1/2)
@@ -1988,7 +2009,23 @@ struct Solver : ISolver {
                                              (const T*)dptr<T>(W.x), dptr<int>(dsrc), ncols, dptr<T>(dvolt)));
         download_cols((const T*)dptr<T>(dvolt), ncols, (T*)volt_out + (size_t)p0 * n_api);
       }
-      if (want_curr) {
+      // lattice path, maps only: the node currents are accumulated where they are computed and never stored
+      const bool accumulate_in_kernel = lattice_maps && !curr_out && (cum_inout || max_inout);
+      if (want_curr && lattice_maps) {
+        size_t part_bytes = 0;
+        CS_DISPATCH_K(K, part_bytes = (size_t)dia_currents_grid<T, KK>(dia) * KK * 2 * sizeof(double));
+        if (dbpart.bytes < part_bytes) dbpart.alloc(part_bytes);
+        if (accumulate_in_kernel) {
+          for (int c = 0; c < K; ++c) w32[c] = c < ncols ? (weights ? weights[p0 + c] : 1) : 0;
+          CS_HIP(hipMemcpyAsync(dweight.p, w32.data(), K * sizeof(int), hipMemcpyHostToDevice, st));
+        }
+        CS_DISPATCH_K(K, dia_branch_max<T, KK>(dia, (const T*)dptr<T>(W.x), dptr<double>(dbpart), dptr<double>(dbmax), st));
+        CS_DISPATCH_K(K, dia_node_currents<T, KK>(dia, (const T*)dptr<T>(W.x), (const double*)dptr<double>(dbmax),
+                                                  accumulate_in_kernel ? (T*)nullptr : dptr<T>(dcurr),
+                                                  cum_inout ? dptr<T>(dcum) : (T*)nullptr, max_inout ? dptr<T>(dmax) : (T*)nullptr,
+                                                  (const int*)dptr<int>(dweight), ncols, st));
+      }
+      if (want_curr && !lattice_maps) {
         const Csr<T>& A = cg_matrix();
         const int gc = grid_for(n * K);
         CS_DISPATCH_K(K, hipLaunchKernelGGL((branch_max_kernel<T, KK>), dim3(gc), dim3(256), 0, st, (int)n, A.rp(), A.ci(),
@@ -1999,7 +2036,11 @@ struct Solver : ISolver {
                                             A.va(), (const T*)dptr<T>(W.x), (const double*)dptr<double>(dbmax),
                                             dptr<T>(dcurr), (const T*)nullptr, (const int*)nullptr,
                                             (const unsigned long long*)nullptr, api_order()));
+      }
+      if (want_curr) {
         if (branch_out) {
+          const Csr<T>& A = cg_matrix();
+          const int gc = grid_for(n * K);
           CS_DISPATCH_K(K, hipLaunchKernelGGL((branch_current_kernel<T, KK>), dim3(gc), dim3(256), 0, st, (int)n, A.rp(), A.ci(),
                                               A.va(), (const T*)dptr<T>(W.x), (const double*)dptr<double>(dbmax),
                                               dptr<T>(dbranch), api_order()));
@@ -2019,7 +2060,7 @@ struct Solver : ISolver {
                                               (const T*)dptr<T>(dcurr), ncols, dptr<T>(dvolt)));
           download_cols((const T*)dptr<T>(dvolt), ncols, (T*)curr_out + (size_t)p0 * n_api);
         }
-        if (cum_inout || max_inout) {
+        if ((cum_inout || max_inout) && !accumulate_in_kernel) {
           for (int c = 0; c < K; ++c) w32[c] = c < ncols ? (weights ? weights[p0 + c] : 1) : 0;
           CS_HIP(hipMemcpyAsync(dweight.p, w32.data(), K * sizeof(int), hipMemcpyHostToDevice, st));
           CS_DISPATCH_K(K, hipLaunchKernelGGL((current_accumulate_kernel<T, KK>), dim3(grid_for(n)), dim3(256), 0, st, (int)n,
@@ -2482,6 +2523,7 @@ struct Solver : ISolver {
     info->virtual_rhs_solves = H.virtual_rhs_solves;
     info->chained_level1_cycles = H.chained_level1_cycles;
     info->reordered = reordered ? 1 : 0;
+    info->csr_built = csr_ready ? 1 : 0;
     info->reorder_ms = reorder_ms;
     info->span_before = span_before;
     info->span_after = span_after;
@@ -3589,6 +3631,7 @@ int csgpu_multi_solve_pairs(csgpu_multi* m, const int64_t* src, const int64_t* d
       st[slot].resid_calls += cs.resid_calls;
       st[slot].resid_bytes = cs.resid_bytes;
       st[slot].resid_fused = cs.resid_fused;
+      st[slot].lattice_maps = std::max(st[slot].lattice_maps, cs.lattice_maps);
       st[slot].batch = std::max(st[slot].batch, cs.batch);
       m->pairs_done[slot] += cnt;
       if (rc != CSGPU_OK && codes[slot] == CSGPU_OK) {
@@ -3620,6 +3663,7 @@ int csgpu_multi_solve_pairs(csgpu_multi* m, const int64_t* src, const int64_t* d
     s->resid_calls += st[i].resid_calls;
     s->resid_bytes = std::max(s->resid_bytes, st[i].resid_bytes);
     s->resid_fused = std::max(s->resid_fused, st[i].resid_fused);
+    s->lattice_maps = std::max(s->lattice_maps, st[i].lattice_maps);
     s->batch = std::max(s->batch, st[i].batch);
     if (codes[i] != CSGPU_OK && (rc_out == CSGPU_OK || rc_out == CSGPU_NOT_CONVERGED)) {
       rc_out = codes[i];
@@ -3713,6 +3757,7 @@ int csgpu_multi_solve_pairs_currents(csgpu_multi* m, const int64_t* src, const i
     s->resid_calls += st[i].resid_calls;
     s->resid_bytes = std::max(s->resid_bytes, st[i].resid_bytes);
     s->resid_fused = std::max(s->resid_fused, st[i].resid_fused);
+    s->lattice_maps = std::max(s->lattice_maps, st[i].lattice_maps);
     s->batch = std::max(s->batch, st[i].batch);
     if (codes[i] != CSGPU_OK && (rc_out == CSGPU_OK || rc_out == CSGPU_NOT_CONVERGED)) {
       rc_out = codes[i];
@@ -3797,6 +3842,7 @@ int multi_grounded(csgpu_multi* m, int64_t nrhs, void* cum_curr_inout, void* max
     s->resid_calls += st[i].resid_calls;
     s->resid_bytes = std::max(s->resid_bytes, st[i].resid_bytes);
     s->resid_fused = std::max(s->resid_fused, st[i].resid_fused);
+    s->lattice_maps = std::max(s->lattice_maps, st[i].lattice_maps);
     s->batch = std::max(s->batch, st[i].batch);
     if (codes[i] != CSGPU_OK && (rc_out == CSGPU_OK || rc_out == CSGPU_NOT_CONVERGED)) {
       rc_out = codes[i];

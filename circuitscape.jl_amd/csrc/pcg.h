@@ -463,6 +463,10 @@ struct PcgParams {
   // Rasters with short-circuit polygons on the lattice path (poly.h): PCG in the subspace of the vectors that are
   // constant on every polygon -- r and z are projected (averaged over each polygon's cells) after every update.
   const PolyProj* proj = nullptr;
+  // need_x on a handle with a lattice form: the explicit post-check takes b - A x from the lattice form (dia_apply) instead of
+  // the CSR product, so the solve touches no CSR array at all (csgpu_opts.lattice_maps). Solves without Dirichlet sets and
+  // without a projection only; every other solve ignores it.
+  bool lattice_check = false;
 };
 
 // One captured chunk of `check_every` PCG iterations. Kernel arguments are baked in at capture time, so a graph is
@@ -625,6 +629,7 @@ struct PcgBatchResult {
   double resid_ms = 0;     // the residual-update launches (with the restriction, on the fused path) of the same iterations
   int64_t resid_calls = 0, resid_bytes = 0;
   int resid_fused = 0;
+  int lattice_check = 0;   // 1 = the explicit post-check took b - A x from the lattice form (PcgParams::lattice_check)
   bool explicit_relres = false;  // s.relres is ||A x - b|| / ||b|| of an explicit product (x carried), not the recurrence residual
 };
 
@@ -1146,7 +1151,8 @@ struct PcgRun {
     k.iters = plan.chunk;
     k.rtol = pp.rtol;
     k.atol = w.atol;
-    k.matrix = (const void*)A.val.p;
+    // (a raster handle without a CSR form has no values there: its lattice rows are what the chunk's kernels read)
+    k.matrix = A.val.p ? (const void*)A.val.p : (plan.use_dia ? (const void*)dia->rows.p : nullptr);
     k.need_x = pp.need_x ? 1 : 0;
     k.nf = plan.nf;
     k.parity = parity | (resid.sel << 1);
@@ -1221,10 +1227,15 @@ struct PcgRun {
     DBuf nrm;                      // block-diagonal systems: per-component norms
     double* worst = nullptr;
     if (pp.need_x) {
-      SpmvArgs<T> a = spmv_args(A, (const T*)x, Ap);
-      a.order = H.levels[0].orderA.p ? dptr<int>(H.levels[0].orderA) : nullptr;
-      a.b = b;
-      spmv_launch<T, K>(a, EPI_RESID, false, st);
+      if (pp.lattice_check && plan.use_dia && !plan.grounded && !plan.projected) {
+        dia_apply<T, K>(*dia, (const T*)x, Ap, b, (const int*)nullptr, st);  // Ap = b - A x, no CSR array read
+        res.lattice_check = 1;
+      } else {
+        SpmvArgs<T> a = spmv_args(A, (const T*)x, Ap);
+        a.order = H.levels[0].orderA.p ? dptr<int>(H.levels[0].orderA) : nullptr;
+        a.b = b;
+        spmv_launch<T, K>(a, EPI_RESID, false, st);
+      }
       if (plan.grounded)  // rows of the grounded nodes are not equations of the reduced system
         hipLaunchKernelGGL((mask_grounds_kernel<T, T, K>), dim3(plan.gm), dim3(256), 0, st, pp.gptr, pp.gidx, Ap, (T*)nullptr,
                            (const int*)nullptr);

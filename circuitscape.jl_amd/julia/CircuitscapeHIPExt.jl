@@ -32,6 +32,9 @@ mutable struct CsgpuOpts
     # that carry the solution (voltages, current maps, costing n x batch more values of device memory), -1 = two passes,
     # 0 = the default (fused for resistance-only fp64 pair solves only)
     collapse_min::Int32; verbose::Int32; expander_probe::Int32; fused_restrict::Int32; sparse_init::Int32; fused_level1::Int32
+    # lattice_maps: 1 = voltage / current maps and explicit_check of pair solves from the lattice form (no CSR matrix), -1 = never,
+    # 0 = only on rasters too large for a CSR form (2^31 stored entries)
+    lattice_maps::Int32
     stream_min::Int64; host_stream_block::Int64
     enrich_tau::Float64; hetero_fp64_frac::Float64; poly_strength::Float64; poly_coef::Float64; poly_smin::Float64
     poly_smax::Float64; cellspace_min_frac::Float64; tile_theta::Float64; tile_split_min::Float64
@@ -42,7 +45,7 @@ mutable struct CsgpuStats
     nrhs::Int32; max_iters::Int32; total_iters::Int64; max_relres::Float64; solve_ms::Float64; device_ms::Float64
     cg_spmv_ms::Float64; cg_spmv_calls::Int64; batch::Int32; not_converged::Int32; graph_launches::Int64; polished_batches::Int64
     cg_spmv_bytes::Int64; stream_slots::Int64
-    resid_ms::Float64; resid_calls::Int64; resid_bytes::Int64; resid_fused::Int32; reserved_stats::Int32
+    resid_ms::Float64; resid_calls::Int64; resid_bytes::Int64; resid_fused::Int32; lattice_maps::Int32
     CsgpuStats() = new(0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0, 0, 0, 0)
 end
 

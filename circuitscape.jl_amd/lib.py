@@ -43,7 +43,8 @@ OPTS_INT_FIELDS = ("last_level_sweeps", "enrich", "enrich_steps", "dia25_min_row
                    "lattice_level1_min_rows", "lattice_setup", "lattice_s", "lattice_q", "direct_tiles", "tile_pieces",
                    "direct_at", "dirichlet_coarse", "deflation", "tail_projection", "coarse_smoother", "nu_l1", "nu_deep",
                    "wide_csr", "fixed_k", "recompute_ap", "longrow", "narrow_tile", "spmv_grid_cap", "dia_seg", "restrict_seg",
-                   "collapse_min", "verbose", "expander_probe", "fused_restrict", "sparse_init", "fused_level1")
+                   "collapse_min", "verbose", "expander_probe", "fused_restrict", "sparse_init", "fused_level1",
+                   "lattice_maps")
 OPTS_DOUBLE_FIELDS = ("enrich_tau", "hetero_fp64_frac", "poly_strength", "poly_coef", "poly_smin", "poly_smax",
                       "cellspace_min_frac", "tile_theta", "tile_split_min")
 
@@ -80,6 +81,7 @@ class Info(ctypes.Structure):
         ("poly_lattice", ctypes.c_int32), ("enrich_on", ctypes.c_int32), ("enrich_tau", ctypes.c_double),
         ("expander_probe_hit", ctypes.c_int32), ("fused_restrict_solves", ctypes.c_int32), ("virtual_rhs_solves", ctypes.c_int32), ("chained_level1_cycles", ctypes.c_int32),
         ("reorder_ms", ctypes.c_double), ("span_before", ctypes.c_double), ("span_after", ctypes.c_double),
+        ("csr_built", ctypes.c_int32),
     ]
 
 
@@ -95,7 +97,7 @@ class Stats(ctypes.Structure):
         ("not_converged", ctypes.c_int32), ("graph_launches", ctypes.c_int64),
         ("polished_batches", ctypes.c_int64), ("cg_spmv_bytes", ctypes.c_int64), ("stream_slots", ctypes.c_int64),
         ("resid_ms", ctypes.c_double), ("resid_calls", ctypes.c_int64), ("resid_bytes", ctypes.c_int64),
-        ("resid_fused", ctypes.c_int32), ("reserved_stats", ctypes.c_int32),
+        ("resid_fused", ctypes.c_int32), ("lattice_maps", ctypes.c_int32),
     ]
 
     def as_dict(self):

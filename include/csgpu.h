@@ -63,8 +63,11 @@
  *     use_64bit_indexing, src/run.jl:34: Int64 colptr / rowval) is accepted by csgpu_setup when it is the graph of a raster
  *     without polygons and comes with csgpu_opts.node_row / node_col: it is streamed to the device in blocks of rows and
  *     scattered straight into the same lattice form (csgpu_get_info().host_blocks tells; status 4 with the reason when the
- *     matrix does not qualify). Calls that need the CSR form of such a handle (voltage / current maps, explicit_check)
- *     return status 4, resistance-only csgpu_solve_pairs does not.
+ *     matrix does not qualify). Pair solves on such a handle need no CSR form whatever they return: voltage maps,
+ *     node-current, cumulative and maximum maps and explicit_check are computed from the lattice form
+ *     (csgpu_opts.lattice_maps; csgpu_stats.lattice_maps = 1, csgpu_info.csr_built stays 0). The calls that still walk a CSR
+ *     form -- csgpu_solve_rhs, csgpu_solve_grounded / _sources, csgpu_solve_raster, region pairs, csgpu_components, the
+ *     product hooks, and every pair solve under lattice_maps = -1 -- return status 4 on a handle of that size.
  *   - All calls are blocking; a handle is serialised internally (one caller at a time per handle).
  *   - Return value: 0 ok, 1 not converged (some right-hand side failed the reference's 1e-4 true-residual check,
  *     src/core.jl:640-641 -- the reference's only acceptance test: how the iteration stopped (rule met, itmax, breakdown of
@@ -262,7 +265,17 @@ typedef struct csgpu_opts {
                                  passes; 0 = library default: 2 in a double-precision hierarchy (-2.2 % of a batch at 10000^2), four
                                  passes in a single-precision one (the chained pass has not been timed there); same bits
                                  whichever runs (csgpu_info.chained_level1_cycles tells) */
-  int64_t stream_min;         /* vector elements n * batch from which streaming is considered, 0 = 2^25 */
+  int32_t lattice_maps;       /* csgpu_solve_pairs with volt_out or explicit_check, csgpu_solve_pairs_currents without branch_out
+                                 (and their csgpu_multi_ twins) on a handle whose CG product runs from the lattice form (rasters
+                                 without polygons; not with csgpu_opts.reorder): 1 = the explicit residual check and the node
+                                 currents are computed from the lattice form (csrc/lattice_currents.h) and no CSR form of the
+                                 fine-level matrix is built or read -- every number returned equals the CSR path's bit for
+                                 bit, except max_relres, whose residual is summed in another order; -1 = never (a raster with
+                                 2^31 stored entries then returns status 4 for these calls); 0 = library default: the CSR
+                                 path wherever the handle can hold a CSR form, the lattice path where it cannot (nnz >= 2^31).
+                                 csgpu_stats.lattice_maps tells which one a call took, csgpu_info.csr_built whether the
+                                 handle holds a CSR form */
+  int64_t stream_min;        /* vector elements n * batch from which streaming is considered, 0 = 2^25 */
   int64_t host_stream_block;  /* csgpu_setup: stream the host matrix in blocks of at most this many entries (test / tuning);
                                  0 = only matrices with >= 2^31 stored entries, in blocks of 2^28 */
   double enrich_tau;          /* local Fiedler value below which an aggregate gets its second function, 0 = 0.06 */
@@ -328,6 +341,8 @@ typedef struct csgpu_info {
                                    lattice / expansion checks that decide whether to reorder); INCLUDED in setup_ms */
   double span_before;           /* reordered handles: mean |col - row| / n over the stored entries of the matrix as given ... */
   double span_after;            /* ... and of the device matrix P A P' (0 when not reordered) */
+  int32_t csr_built;            /* 1 while the device holds a CSR form of the fine-level matrix (a raster handle builds it on the
+                                   first call that needs it; csgpu_opts.lattice_maps) */
 } csgpu_info;
 
 typedef struct csgpu_stats {
@@ -360,7 +375,8 @@ typedef struct csgpu_stats {
                                    figure does NOT count x, which its update reads and writes as well when the solution is
                                    carried). 0 when the update is not the lattice kernel */
   int32_t resid_fused;          /* 1 = those launches are the fused residual update + restriction (csgpu_opts.fused_restrict) */
-  int32_t reserved_stats;
+  int32_t lattice_maps;         /* 1 = this call's explicit post-check and current kernels ran from the lattice form
+                                   (csgpu_opts.lattice_maps); 0 = from the CSR form, or the call needed neither */
 } csgpu_stats;
 
 int csgpu_device_count(void);
