@@ -1635,16 +1635,12 @@ struct Solver : ISolver {
   // ONE block-diagonal system, solved by ONE PCG). curr_out / volt_out: row-major rasters, 0 where there is no node.
   void solve_raster(const void* source, void* curr_out, void* volt_out, csgpu_stats* stats) override {
     if (poly_proj) return poly_fallback().solve_raster(source, curr_out, volt_out, stats);
-    std::lock_guard<std::mutex> lk(mu);
-    KnobScope ks(&kn);
-    CS_HIP(hipSetDevice(device));
-    auto t0 = std::chrono::steady_clock::now();
-    if (stats) memset(stats, 0, sizeof(*stats));
+    CallScope call(*this, stats);
     CS_REQUIRE(nodemap.p != nullptr, CSGPU_BAD_ARGS, "handle was not built by csgpu_raster_setup");
     const int64_t ncells = raster_rows * raster_cols;
     ensure_csr();
     ensure_components();
-    W.ensure(n, 1, H.levels.size() > 1 && H.levels[0].two_product() ? H.levels[1].A.nrows : 0);
+    W.ensure(n, 1, tail_rows());
     if (stats) {
       stats->nrhs = 1;
       stats->batch = 1;
@@ -1702,7 +1698,7 @@ struct Solver : ISolver {
       CS_HIP(hipStreamSynchronize(st));
     }
     check_launch("solve_raster");
-    if (stats) stats->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    call.done();
   }
 
   int pick_k(int64_t ncols) const {
@@ -1738,16 +1734,33 @@ struct Solver : ISolver {
     }
     return pcg_solve<T, TP, K>(cg_matrix(), H, W, pp, ncols, st, dia_ptr());
   }
+#define CS_DISPATCH_K(K, ...)                               \
+  switch (K) {                                              \
+    case 1: { constexpr int KK = 1; __VA_ARGS__; } break;   \
+    case 2: { constexpr int KK = 2; __VA_ARGS__; } break;   \
+    case 4: { constexpr int KK = 4; __VA_ARGS__; } break;   \
+    case 8: { constexpr int KK = 8; __VA_ARGS__; } break;   \
+    case 32: { constexpr int KK = 32; __VA_ARGS__; } break; \
+    default: { constexpr int KK = 16; __VA_ARGS__; } break; \
+  }
+
   PcgBatchResult run_batch_k(int K, int ncols, bool need_x = true, const double* bb_host = nullptr,
                              const int* pair_src = nullptr, const int* pair_dst = nullptr, bool lattice_check = false) {
-    switch (K) {
-      case 1: return run_batch<1>(ncols, need_x, bb_host, pair_src, pair_dst, lattice_check);
-      case 2: return run_batch<2>(ncols, need_x, bb_host, pair_src, pair_dst, lattice_check);
-      case 4: return run_batch<4>(ncols, need_x, bb_host, pair_src, pair_dst, lattice_check);
-      case 8: return run_batch<8>(ncols, need_x, bb_host, pair_src, pair_dst, lattice_check);
-      case 32: return run_batch<32>(ncols, need_x, bb_host, pair_src, pair_dst, lattice_check);
-      default: return run_batch<16>(ncols, need_x, bb_host, pair_src, pair_dst, lattice_check);
-    }
+    PcgBatchResult r;
+    CS_DISPATCH_K(K, r = run_batch<KK>(ncols, need_x, bb_host, pair_src, pair_dst, lattice_check));
+    return r;
+  }
+
+  // a PCG batch with per-column Dirichlet sets: column c is masked on the rows gidx[gptr[c] .. gptr[c + 1]) (device lists)
+  PcgBatchResult run_masked_batch_k(int K, int ncols, const DBuf& dgp, const DBuf& dgi, int gtotal) {
+    PcgParams pp = pcg_params(K);
+    pp.need_x = true;
+    pp.gptr = dptr<int>(dgp);
+    pp.gidx = dptr<int>(dgi);
+    pp.gtotal = gtotal;
+    PcgBatchResult r;
+    CS_DISPATCH_K(K, r = (pcg_solve<T, TP, KK>(cg_matrix(), H, W, pp, ncols, st, dia_ptr())));
+    return r;
   }
 
   // streaming pair solves (pcg_stream_pairs, pcg.h) for the wide batches
@@ -1762,20 +1775,22 @@ struct Solver : ISolver {
     }
   }
 
+  // one column's outcome (a column of a batch, a pair of the stream) into the call's stats
+  static void accumulate_column(csgpu_stats* s, int iters, double relres, int done, bool explicit_relres) {
+    s->total_iters += iters;
+    s->max_iters = std::max(s->max_iters, iters);
+    s->max_relres = std::max(s->max_relres, relres);
+    // the reference's ONLY acceptance test is the residual (src/core.jl:639-641: Krylov.cg's stats are not looked at): a
+    // column that stopped on itmax or on a breakdown of the recurrence with ||Ax-b||/||b|| < 1e-4 is a success there, and
+    // here (fuzz finding of round 5: ten-decade mazes at rtol 1e-10 stagnate at 1e-7 and were reported as failures)
+    // (... with two decades of margin where the figure is the recurrence residual of a column that did not stop on the
+    // rule: column_accepted, pcg.h)
+    if (!column_accepted(relres, done, explicit_relres)) s->not_converged += 1;
+  }
+
   void accumulate(csgpu_stats* s, const PcgBatchResult& r, int ncols) {
     if (!s) return;
-    for (int c = 0; c < ncols; ++c) {
-      s->total_iters += r.s.iters[c];
-      s->max_iters = std::max(s->max_iters, r.s.iters[c]);
-      s->max_relres = std::max(s->max_relres, r.s.relres[c]);
-      // the reference's ONLY acceptance test is the residual (src/core.jl:639-641: Krylov.cg's stats are not looked at): a
-      // column that stopped on itmax or on a breakdown of the recurrence with ||Ax-b||/||b|| < 1e-4 is a success there, and
-      // here (fuzz finding of round 5: ten-decade mazes at rtol 1e-10 stagnate at 1e-7 and were reported as failures)
-      // (... with two decades of margin where the figure is the recurrence residual of a column that did not stop on the
-      // rule: column_accepted, pcg.h)
-      const bool bad = !column_accepted(r.s.relres[c], r.s.done[c], r.explicit_relres);
-      if (bad) s->not_converged += 1;
-    }
+    for (int c = 0; c < ncols; ++c) accumulate_column(s, r.s.iters[c], r.s.relres[c], r.s.done[c], r.explicit_relres);
     s->device_ms += r.device_ms;
     s->cg_spmv_ms += r.spmv_ms;
     s->cg_spmv_calls += r.spmv_calls;
@@ -1788,15 +1803,96 @@ struct Solver : ISolver {
     s->resid_fused = r.resid_fused;
   }
 
-#define CS_DISPATCH_K(K, ...)                               \
-  switch (K) {                                              \
-    case 1: { constexpr int KK = 1; __VA_ARGS__; } break;   \
-    case 2: { constexpr int KK = 2; __VA_ARGS__; } break;   \
-    case 4: { constexpr int KK = 4; __VA_ARGS__; } break;   \
-    case 8: { constexpr int KK = 8; __VA_ARGS__; } break;   \
-    case 32: { constexpr int KK = 32; __VA_ARGS__; } break; \
-    default: { constexpr int KK = 16; __VA_ARGS__; } break; \
-  }
+  // rows of the tail arena the two-product level 0 asks of the work buffers (PcgWork::ensure)
+  int64_t tail_rows() const { return H.levels.size() > 1 && H.levels[0].two_product() ? H.levels[1].A.nrows : 0; }
+
+  // What every solve method opens with, in this order: the handle's lock, its knobs for the calling thread, its device, the
+  // start time, zeroed stats. done() writes solve_ms -- a line of its own at the end of a method, so that a call that throws
+  // or returns early leaves it at 0.
+  struct CallScope {
+    std::lock_guard<std::mutex> lk;
+    KnobScope ks;
+    std::chrono::steady_clock::time_point t0;
+    csgpu_stats* stats;
+    CallScope(Solver& s, csgpu_stats* stats_) : lk(s.mu), ks(&s.kn), stats(stats_) {
+      CS_HIP(hipSetDevice(s.device));
+      t0 = std::chrono::steady_clock::now();
+      if (stats) memset(stats, 0, sizeof(*stats));
+    }
+    void done() const {
+      if (stats) stats->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+  };
+
+  // The node-current buffers of one solve_pairs / solve_grounded call: the currents of a batch (dcurr, interleaved n x K), the
+  // per-block and per-column branch maxima behind the drop threshold (dbpart, dbmax), the columns' weights, and the
+  // cumulative / maximum maps of the call (dcum, dmax), which finish() folds into the caller's arrays.
+  struct CurrentMaps {
+    Solver& S;
+    void *cum_inout = nullptr, *max_inout = nullptr;
+    DBuf dcurr, dbpart, dbmax, dweight, dcum, dmax;
+    std::vector<int> w32;
+    explicit CurrentMaps(Solver& s) : S(s) {}
+    // lattice: the currents come from lattice_currents.h -- dcurr only if they are stored at all, dbpart sized per batch by the
+    // caller; otherwise (CSR) dbpart holds the partial maxima of the largest grid. with_weights: dweight is wanted.
+    void alloc(int Kmax, bool lattice, bool store_curr, bool with_weights, void* cum, void* mx) {
+      cum_inout = cum;
+      max_inout = mx;
+      w32.resize(Kmax);
+      if (!lattice || store_curr) dcurr.alloc((size_t)S.n * Kmax * sizeof(T));
+      if (with_weights) dweight.alloc((size_t)Kmax * sizeof(int));
+      if (!lattice) dbpart.alloc((size_t)kMaxGrid * Kmax * 2 * sizeof(double));
+      dbmax.alloc((size_t)Kmax * 2 * sizeof(double));
+      auto zeroed = [&](DBuf& d) {
+        d.alloc((size_t)S.n * sizeof(T));
+        CS_HIP(hipMemsetAsync(d.p, 0, d.bytes, S.st));
+      };
+      if (cum) zeroed(dcum);
+      if (mx) zeroed(dmax);
+    }
+    T* cum() const { return cum_inout ? dptr<T>(dcum) : (T*)nullptr; }
+    T* mx() const { return max_inout ? dptr<T>(dmax) : (T*)nullptr; }
+    // node currents of the batch in W.x from the CSR form (currents.h)
+    void csr_node_currents(int K) {
+      const Csr<T>& A = S.cg_matrix();
+      const int n = (int)S.n, gc = grid_for(S.n * K);
+      const T* x = dptr<T>(S.W.x);
+      hipStream_t st = S.st;
+      CS_DISPATCH_K(K, hipLaunchKernelGGL((branch_max_kernel<T, KK>), dim3(gc), dim3(256), 0, st, n, A.rp(), A.ci(), A.va(), x,
+                                          dptr<double>(dbpart), S.api_order()));
+      CS_DISPATCH_K(K, hipLaunchKernelGGL((branch_max_final_kernel<KK>), dim3(1), dim3(256), 0, st,
+                                          (const double*)dptr<double>(dbpart), gc, dptr<double>(dbmax)));
+      CS_DISPATCH_K(K, hipLaunchKernelGGL((node_current_kernel<T, KK>), dim3(gc), dim3(256), 0, st, n, A.rp(), A.ci(), A.va(), x,
+                                          (const double*)dptr<double>(dbmax), dptr<T>(dcurr), (const T*)nullptr,
+                                          (const int*)nullptr, (const unsigned long long*)nullptr, S.api_order()));
+    }
+    // the weights of the batch's columns (weights == NULL: 1 each; 0 for the idle columns of a short batch)
+    void upload_weights(int K, int ncols, const int32_t* weights) {
+      for (int c = 0; c < K; ++c) w32[c] = c < ncols ? (weights ? weights[c] : 1) : 0;
+      CS_HIP(hipMemcpyAsync(dweight.p, w32.data(), K * sizeof(int), hipMemcpyHostToDevice, S.st));
+    }
+    // dcurr of the batch into the cumulative / maximum maps
+    void accumulate(int K, int ncols, const int32_t* weights) {
+      upload_weights(K, ncols, weights);
+      CS_DISPATCH_K(K, hipLaunchKernelGGL((current_accumulate_kernel<T, KK>), dim3(grid_for(S.n)), dim3(256), 0, S.st, (int)S.n,
+                                          (const T*)dptr<T>(dcurr), ncols, (const int*)dptr<int>(dweight), cum(), mx()));
+    }
+    // end of the call: += / max into the caller's arrays (caller's numbering)
+    void finish() {
+      if (!cum_inout && !max_inout) return;
+      std::vector<T> tmp((size_t)S.n_api);
+      if (cum_inout) {
+        S.download_cols((const T*)dptr<T>(dcum), 1, tmp.data());
+        T* h = (T*)cum_inout;
+        for (int64_t i = 0; i < S.n_api; ++i) h[i] += tmp[i];
+      }
+      if (max_inout) {
+        S.download_cols((const T*)dptr<T>(dmax), 1, tmp.data());
+        T* h = (T*)max_inout;
+        for (int64_t i = 0; i < S.n_api; ++i) h[i] = tmp[i] > h[i] ? tmp[i] : h[i];
+      }
+    }
+  };
 
   void solve_pairs(const int64_t* src, const int64_t* dst, int64_t npairs, void* volt_out, const int64_t* gather,
                    int64_t ngather, void* gathered_out, void* resist_out, csgpu_stats* stats, const int32_t* weights,
@@ -1806,11 +1902,7 @@ struct Solver : ISolver {
     if (poly_proj && (volt_out || curr_out || cum_inout || max_inout || branch_out || opts.explicit_check > 0))
       return poly_fallback().solve_pairs(src, dst, npairs, volt_out, gather, ngather, gathered_out, resist_out, stats, weights,
                                          curr_out, cum_inout, max_inout, branch_out);
-    std::lock_guard<std::mutex> lk(mu);
-    KnobScope ks(&kn);
-    CS_HIP(hipSetDevice(device));
-    auto t0 = std::chrono::steady_clock::now();
-    if (stats) memset(stats, 0, sizeof(*stats));
+    CallScope call(*this, stats);
     for (int64_t p = 0; p < npairs; ++p)
       CS_REQUIRE(src[p] >= 0 && src[p] < n_api && dst[p] >= 0 && dst[p] < n_api, CSGPU_BAD_ARGS, "pair node id out of range");
     for (int64_t g = 0; g < ngather; ++g)
@@ -1843,8 +1935,7 @@ struct Solver : ISolver {
     // every K = 32 pass -- 0.6 s of the 2.66 s job at 10000^2; the reference's batched driver handles a
     // short last batch too, src/core.jl:448-463).
     const int Kmax = pick_k(npairs);
-    const int64_t tail_rows = H.levels.size() > 1 && H.levels[0].two_product() ? H.levels[1].A.nrows : 0;
-    W.ensure(n, Kmax, tail_rows);
+    W.ensure(n, Kmax, tail_rows());
     if (stats) {
       stats->nrhs = (int)npairs;
       stats->batch = Kmax;
@@ -1872,12 +1963,7 @@ struct Solver : ISolver {
                                         gathered_out ? (T*)gathered_out + (size_t)p0 * ngather : (T*)nullptr);
       if (!sr.applicable) return false;
       if (stats) {
-        for (size_t p = 0; p < sr.iters.size(); ++p) {
-          stats->total_iters += sr.iters[p];
-          stats->max_iters = std::max(stats->max_iters, sr.iters[p]);
-          stats->max_relres = std::max(stats->max_relres, sr.relres[p]);
-          if (!column_accepted(sr.relres[p], sr.status[p], false)) stats->not_converged += 1;   // (as in accumulate())
-        }
+        for (size_t p = 0; p < sr.iters.size(); ++p) accumulate_column(stats, sr.iters[p], sr.relres[p], sr.status[p], false);
         stats->device_ms += sr.device_ms;
         stats->cg_spmv_ms += sr.spmv_ms;
         stats->cg_spmv_calls += sr.spmv_calls;
@@ -1911,7 +1997,8 @@ struct Solver : ISolver {
     if (stats) stats->lattice_maps = lattice_maps ? 1 : 0;
     std::vector<int> focal;
     if (!need_x) focal.resize((size_t)ngather + 2 * Kmax);
-    DBuf dcurr, dcum, dmax, dweight, dbpart, dbmax, dbranch, dbranch2;
+    DBuf dbranch, dbranch2;
+    CurrentMaps M(*this);
     if (branch_out) {
       if (reordered && !entry_map.p)
         build_entry_map(cg_matrix(), (const int*)dptr<int>(node2cell), (const int*)dptr<int>(cell2node), entry_map, st);
@@ -1921,20 +2008,9 @@ struct Solver : ISolver {
     if (want_curr) {
       // (lattice path: the currents are stored only when the caller wants them -- the cumulative / maximum maps are accumulated
       // inside the kernel -- and the partial maxima are sized per batch from that launch's grid)
-      if (!lattice_maps || curr_out) dcurr.alloc((size_t)n * Kmax * sizeof(T));
-      dweight.alloc((size_t)Kmax * sizeof(int));
-      if (!lattice_maps) dbpart.alloc((size_t)kMaxGrid * Kmax * 2 * sizeof(double));
-      dbmax.alloc((size_t)Kmax * 2 * sizeof(double));
-      if (cum_inout) {
-        dcum.alloc((size_t)n * sizeof(T));
-        CS_HIP(hipMemsetAsync(dcum.p, 0, dcum.bytes, st));
-      }
-      if (max_inout) {
-        dmax.alloc((size_t)n * sizeof(T));
-        CS_HIP(hipMemsetAsync(dmax.p, 0, dmax.bytes, st));
-      }
+      M.alloc(Kmax, lattice_maps, /*store_curr=*/curr_out != nullptr, /*with_weights=*/true, cum_inout, max_inout);
     }
-    std::vector<int> s32(Kmax), d32(Kmax), w32(Kmax);
+    std::vector<int> s32(Kmax), d32(Kmax);
     const bool fixed_k = kn.fixed_k;  // A/B knob (csgpu_opts.fixed_k): every batch at the call's width (round 5)
     int K = Kmax;
     for (int64_t p0 = 0; p0 < npairs; p0 += K) {
@@ -1943,7 +2019,7 @@ struct Solver : ISolver {
         stream_now = stream_eligible = false;  // (declined: not asked again in this call)
       }
       K = fixed_k ? Kmax : pick_k(npairs - p0);
-      W.ensure(n, K, tail_rows);  // (a narrower batch: same buffers, laid out for its own width)
+      W.ensure(n, K, tail_rows());  // (a narrower batch: same buffers, laid out for its own width)
       const int ncols = (int)std::min<int64_t>(K, npairs - p0);
       for (int c = 0; c < K; ++c) {
         s32[c] = (int)src[p0 + std::min(c, ncols - 1)];
@@ -2014,35 +2090,20 @@ struct Solver : ISolver {
       if (want_curr && lattice_maps) {
         size_t part_bytes = 0;
         CS_DISPATCH_K(K, part_bytes = (size_t)dia_currents_grid<T, KK>(dia) * KK * 2 * sizeof(double));
-        if (dbpart.bytes < part_bytes) dbpart.alloc(part_bytes);
-        if (accumulate_in_kernel) {
-          for (int c = 0; c < K; ++c) w32[c] = c < ncols ? (weights ? weights[p0 + c] : 1) : 0;
-          CS_HIP(hipMemcpyAsync(dweight.p, w32.data(), K * sizeof(int), hipMemcpyHostToDevice, st));
-        }
-        CS_DISPATCH_K(K, dia_branch_max<T, KK>(dia, (const T*)dptr<T>(W.x), dptr<double>(dbpart), dptr<double>(dbmax), st));
-        CS_DISPATCH_K(K, dia_node_currents<T, KK>(dia, (const T*)dptr<T>(W.x), (const double*)dptr<double>(dbmax),
-                                                  accumulate_in_kernel ? (T*)nullptr : dptr<T>(dcurr),
-                                                  cum_inout ? dptr<T>(dcum) : (T*)nullptr, max_inout ? dptr<T>(dmax) : (T*)nullptr,
-                                                  (const int*)dptr<int>(dweight), ncols, st));
+        if (M.dbpart.bytes < part_bytes) M.dbpart.alloc(part_bytes);
+        if (accumulate_in_kernel) M.upload_weights(K, ncols, weights ? weights + p0 : nullptr);
+        CS_DISPATCH_K(K, dia_branch_max<T, KK>(dia, (const T*)dptr<T>(W.x), dptr<double>(M.dbpart), dptr<double>(M.dbmax), st));
+        CS_DISPATCH_K(K, dia_node_currents<T, KK>(dia, (const T*)dptr<T>(W.x), (const double*)dptr<double>(M.dbmax),
+                                                  accumulate_in_kernel ? (T*)nullptr : dptr<T>(M.dcurr), M.cum(), M.mx(),
+                                                  (const int*)dptr<int>(M.dweight), ncols, st));
       }
-      if (want_curr && !lattice_maps) {
-        const Csr<T>& A = cg_matrix();
-        const int gc = grid_for(n * K);
-        CS_DISPATCH_K(K, hipLaunchKernelGGL((branch_max_kernel<T, KK>), dim3(gc), dim3(256), 0, st, (int)n, A.rp(), A.ci(),
-                                            A.va(), (const T*)dptr<T>(W.x), dptr<double>(dbpart), api_order()));
-        CS_DISPATCH_K(K, hipLaunchKernelGGL((branch_max_final_kernel<KK>), dim3(1), dim3(256), 0, st,
-                                            (const double*)dptr<double>(dbpart), gc, dptr<double>(dbmax)));
-        CS_DISPATCH_K(K, hipLaunchKernelGGL((node_current_kernel<T, KK>), dim3(gc), dim3(256), 0, st, (int)n, A.rp(), A.ci(),
-                                            A.va(), (const T*)dptr<T>(W.x), (const double*)dptr<double>(dbmax),
-                                            dptr<T>(dcurr), (const T*)nullptr, (const int*)nullptr,
-                                            (const unsigned long long*)nullptr, api_order()));
-      }
+      if (want_curr && !lattice_maps) M.csr_node_currents(K);
       if (want_curr) {
         if (branch_out) {
           const Csr<T>& A = cg_matrix();
           const int gc = grid_for(n * K);
           CS_DISPATCH_K(K, hipLaunchKernelGGL((branch_current_kernel<T, KK>), dim3(gc), dim3(256), 0, st, (int)n, A.rp(), A.ci(),
-                                              A.va(), (const T*)dptr<T>(W.x), (const double*)dptr<double>(dbmax),
+                                              A.va(), (const T*)dptr<T>(W.x), (const double*)dptr<double>(M.dbmax),
                                               dptr<T>(dbranch), api_order()));
           CS_DISPATCH_K(K, hipLaunchKernelGGL((deinterleave_kernel<T, KK>), dim3(grid_for(nnz * ncols)), dim3(256), 0, st, nnz,
                                               (const T*)dptr<T>(dbranch), ncols, dptr<T>(dbranch2)));
@@ -2057,46 +2118,24 @@ struct Solver : ISolver {
         }
         if (curr_out) {
           CS_DISPATCH_K(K, hipLaunchKernelGGL((deinterleave_kernel<T, KK>), dim3(grid_for(n * ncols)), dim3(256), 0, st, n,
-                                              (const T*)dptr<T>(dcurr), ncols, dptr<T>(dvolt)));
+                                              (const T*)dptr<T>(M.dcurr), ncols, dptr<T>(dvolt)));
           download_cols((const T*)dptr<T>(dvolt), ncols, (T*)curr_out + (size_t)p0 * n_api);
         }
-        if ((cum_inout || max_inout) && !accumulate_in_kernel) {
-          for (int c = 0; c < K; ++c) w32[c] = c < ncols ? (weights ? weights[p0 + c] : 1) : 0;
-          CS_HIP(hipMemcpyAsync(dweight.p, w32.data(), K * sizeof(int), hipMemcpyHostToDevice, st));
-          CS_DISPATCH_K(K, hipLaunchKernelGGL((current_accumulate_kernel<T, KK>), dim3(grid_for(n)), dim3(256), 0, st, (int)n,
-                                              (const T*)dptr<T>(dcurr), ncols, (const int*)dptr<int>(dweight),
-                                              cum_inout ? dptr<T>(dcum) : (T*)nullptr, max_inout ? dptr<T>(dmax) : (T*)nullptr));
-        }
+        if ((cum_inout || max_inout) && !accumulate_in_kernel) M.accumulate(K, ncols, weights ? weights + p0 : nullptr);
       }
       check_launch("solve_pairs batch");
       CS_HIP(hipStreamSynchronize(st));
     }
-    if (cum_inout || max_inout) {
-      std::vector<T> tmp((size_t)n_api);
-      if (cum_inout) {
-        download_cols((const T*)dptr<T>(dcum), 1, tmp.data());
-        T* h = (T*)cum_inout;
-        for (int64_t i = 0; i < n_api; ++i) h[i] += tmp[i];
-      }
-      if (max_inout) {
-        download_cols((const T*)dptr<T>(dmax), 1, tmp.data());
-        T* h = (T*)max_inout;
-        for (int64_t i = 0; i < n_api; ++i) h[i] = tmp[i] > h[i] ? tmp[i] : h[i];
-      }
-    }
-    if (stats) stats->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    M.finish();
+    call.done();
   }
 
   void solve_rhs(const void* rhs, int64_t nrhs, void* x_out, csgpu_stats* stats) override {
     if (poly_proj) return poly_fallback().solve_rhs(rhs, nrhs, x_out, stats);
-    std::lock_guard<std::mutex> lk(mu);
-    KnobScope ks(&kn);
-    CS_HIP(hipSetDevice(device));
-    auto t0 = std::chrono::steady_clock::now();
-    if (stats) memset(stats, 0, sizeof(*stats));
+    CallScope call(*this, stats);
     const int K = pick_k(nrhs);
     ensure_csr();
-    W.ensure(n, K, H.levels.size() > 1 && H.levels[0].two_product() ? H.levels[1].A.nrows : 0);
+    W.ensure(n, K, tail_rows());
     if (stats) {
       stats->nrhs = (int)nrhs;
       stats->batch = K;
@@ -2114,17 +2153,13 @@ struct Solver : ISolver {
       check_launch("solve_rhs batch");
       download_cols((const T*)dptr<T>(stage), ncols, (T*)x_out + (size_t)p0 * n_api);
     }
-    if (stats) stats->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    call.done();
   }
 
   // N2: per-column Dirichlet sets on one hierarchy (see csgpu_solve_grounded / csgpu_solve_sources in csgpu.h)
   void solve_grounded(const GroundedJob& J, int64_t nrhs, csgpu_stats* stats) override {
     if (poly_proj) return poly_fallback().solve_grounded(J, nrhs, stats);
-    std::lock_guard<std::mutex> lk(mu);
-    KnobScope ks(&kn);
-    CS_HIP(hipSetDevice(device));
-    auto t0 = std::chrono::steady_clock::now();
-    if (stats) memset(stats, 0, sizeof(*stats));
+    CallScope call(*this, stats);
     const int64_t* gptr = J.gptr;
     const int64_t* gidx = J.gidx;
     const int64_t* sptr = J.sptr;
@@ -2158,8 +2193,7 @@ struct Solver : ISolver {
     const int Kmax = pick_k(nrhs);  // (the arena's width; the ragged last batch runs at its own, as in solve_pairs)
     const bool want_curr = J.curr_out || J.cum_inout || J.max_inout;
     ensure_csr();
-    const int64_t tail_rows = H.levels.size() > 1 && H.levels[0].two_product() ? H.levels[1].A.nrows : 0;
-    W.ensure(n, Kmax, tail_rows);
+    W.ensure(n, Kmax, tail_rows());
     W.drop_graphs();  // captured chunks hold the ground-set buffers of an earlier call
     if (stats) {
       stats->nrhs = (int)nrhs;
@@ -2182,22 +2216,10 @@ struct Solver : ISolver {
       dchk = dalloc<int>(Kmax);
       dchkv = dalloc<T>(Kmax);
     }
-    DBuf dcurr, dbpart, dbmax, dcum, dmax, dweight;
-    if (want_curr) {
-      dcurr.alloc((size_t)n * Kmax * sizeof(T));
-      dbpart.alloc((size_t)kMaxGrid * Kmax * 2 * sizeof(double));
-      dbmax.alloc((size_t)Kmax * 2 * sizeof(double));
-      if (J.cum_inout || J.max_inout) dweight.alloc((size_t)Kmax * sizeof(int));
-      if (J.cum_inout) {
-        dcum.alloc((size_t)n * sizeof(T));
-        CS_HIP(hipMemsetAsync(dcum.p, 0, dcum.bytes, st));
-      }
-      if (J.max_inout) {
-        dmax.alloc((size_t)n * sizeof(T));
-        CS_HIP(hipMemsetAsync(dmax.p, 0, dmax.bytes, st));
-      }
-    }
-    std::vector<int> hp(Kmax + 1), hi, srow, scol, w32(Kmax), c32(Kmax);
+    CurrentMaps M(*this);  // (CSR form: the partial maxima at kMaxGrid; the weights only where a map is accumulated)
+    if (want_curr)
+      M.alloc(Kmax, /*lattice=*/false, /*store_curr=*/true, /*with_weights=*/J.cum_inout || J.max_inout, J.cum_inout, J.max_inout);
+    std::vector<int> hp(Kmax + 1), hi, srow, scol, c32(Kmax);
     std::vector<T> sval, chkv(Kmax);
     struct Ent {
       int col, row;
@@ -2209,7 +2231,7 @@ struct Solver : ISolver {
     for (int64_t p0 = 0; p0 < nrhs; p0 += K) {
       K = fixed_k ? Kmax : pick_k(nrhs - p0);
       if (K != W.K) {
-        W.ensure(n, K, tail_rows);
+        W.ensure(n, K, tail_rows());
         W.drop_graphs();
       }
       const int ncols = (int)std::min<int64_t>(K, nrhs - p0);
@@ -2263,15 +2285,7 @@ struct Solver : ISolver {
                                              (const int*)dptr<int>(dgp), (const int*)dptr<int>(dgi), W.rhs(),
                                              (T*)nullptr, (const int*)nullptr));
       CS_HIP(hipStreamSynchronize(st));  // hp / hi / the entry lists are reused by the next batch
-      PcgBatchResult r;
-      {
-        PcgParams pp = pcg_params(K);
-        pp.need_x = true;
-        pp.gptr = dptr<int>(dgp);
-        pp.gidx = dptr<int>(dgi);
-        pp.gtotal = gtotal;
-        CS_DISPATCH_K(K, r = (pcg_solve<T, TP, KK>(cg_matrix(), H, W, pp, ncols, st, dia_ptr())));
-      }
+      PcgBatchResult r = run_masked_batch_k(K, ncols, dgp, dgi, gtotal);
       accumulate(stats, r, ncols);
       if (J.check && J.check_out) {
         for (int c = 0; c < K; ++c) c32[c] = (c < ncols && J.check[p0 + c] >= 0) ? (int)chk_r[p0 + c] : -1;
@@ -2288,49 +2302,21 @@ struct Solver : ISolver {
         download_cols((const T*)dptr<T>(stage), ncols, (T*)J.x_out + (size_t)p0 * n_api);
       }
       if (want_curr) {
-        const Csr<T>& A = cg_matrix();
-        const int gc = grid_for(n * K);
-        CS_DISPATCH_K(K, hipLaunchKernelGGL((branch_max_kernel<T, KK>), dim3(gc), dim3(256), 0, st, (int)n, A.rp(), A.ci(),
-                                            A.va(), (const T*)dptr<T>(W.x), dptr<double>(dbpart), api_order()));
-        CS_DISPATCH_K(K, hipLaunchKernelGGL((branch_max_final_kernel<KK>), dim3(1), dim3(256), 0, st,
-                                            (const double*)dptr<double>(dbpart), gc, dptr<double>(dbmax)));
-        CS_DISPATCH_K(K, hipLaunchKernelGGL((node_current_kernel<T, KK>), dim3(gc), dim3(256), 0, st, (int)n, A.rp(), A.ci(),
-                                            A.va(), (const T*)dptr<T>(W.x), (const double*)dptr<double>(dbmax),
-                                            dptr<T>(dcurr), (const T*)nullptr, (const int*)nullptr,
-                                            (const unsigned long long*)nullptr, api_order()));
+        M.csr_node_currents(K);
         if (J.curr_out) {
           CS_HIP(hipStreamSynchronize(st));  // stage still feeds the copy of x
           CS_DISPATCH_K(K, hipLaunchKernelGGL((deinterleave_kernel<T, KK>), dim3(grid_for(n * ncols)), dim3(256), 0, st, n,
-                                              (const T*)dptr<T>(dcurr), ncols, dptr<T>(stage)));
+                                              (const T*)dptr<T>(M.dcurr), ncols, dptr<T>(stage)));
           download_cols((const T*)dptr<T>(stage), ncols, (T*)J.curr_out + (size_t)p0 * n_api);
         }
-        if (J.cum_inout || J.max_inout) {
-          // the reference's serial merge after the fan-out over the focal points (src/raster/onetoall.jl:153-158)
-          for (int c = 0; c < K; ++c) w32[c] = c < ncols ? 1 : 0;
-          CS_HIP(hipMemcpyAsync(dweight.p, w32.data(), K * sizeof(int), hipMemcpyHostToDevice, st));
-          CS_DISPATCH_K(K, hipLaunchKernelGGL((current_accumulate_kernel<T, KK>), dim3(grid_for(n)), dim3(256), 0, st, (int)n,
-                                              (const T*)dptr<T>(dcurr), ncols, (const int*)dptr<int>(dweight),
-                                              J.cum_inout ? dptr<T>(dcum) : (T*)nullptr,
-                                              J.max_inout ? dptr<T>(dmax) : (T*)nullptr));
-        }
+        // the reference's serial merge after the fan-out over the focal points (src/raster/onetoall.jl:153-158)
+        if (J.cum_inout || J.max_inout) M.accumulate(K, ncols, nullptr);
       }
       check_launch("solve_grounded batch");
       CS_HIP(hipStreamSynchronize(st));
     }
-    if (J.cum_inout || J.max_inout) {
-      std::vector<T> tmp((size_t)n_api);
-      if (J.cum_inout) {
-        download_cols((const T*)dptr<T>(dcum), 1, tmp.data());
-        T* h = (T*)J.cum_inout;
-        for (int64_t i = 0; i < n_api; ++i) h[i] += tmp[i];
-      }
-      if (J.max_inout) {
-        download_cols((const T*)dptr<T>(dmax), 1, tmp.data());
-        T* h = (T*)J.max_inout;
-        for (int64_t i = 0; i < n_api; ++i) h[i] = tmp[i] > h[i] ? tmp[i] : h[i];
-      }
-    }
-    if (stats) stats->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    M.finish();
+    call.done();
   }
 
   // Effective resistance between short-circuited node sets on ONE hierarchy (see csgpu_solve_region_pairs in csgpu.h):
@@ -2339,11 +2325,7 @@ struct Solver : ISolver {
   void solve_region_pairs(const int64_t* set_ptr, const int64_t* set_nodes, int64_t nsets, const int64_t* src_set,
                           const int64_t* dst_set, int64_t npairs, double* resistances, csgpu_stats* stats) override {
     if (poly_proj) return poly_fallback().solve_region_pairs(set_ptr, set_nodes, nsets, src_set, dst_set, npairs, resistances, stats);
-    std::lock_guard<std::mutex> lk(mu);
-    KnobScope ks(&kn);
-    CS_HIP(hipSetDevice(device));
-    auto t0 = std::chrono::steady_clock::now();
-    if (stats) memset(stats, 0, sizeof(*stats));
+    CallScope call(*this, stats);
     for (int64_t q = 0; q < nsets; ++q) {
       CS_REQUIRE(set_ptr[q] <= set_ptr[q + 1], CSGPU_BAD_ARGS, "set_ptr must be non-decreasing");
       for (int64_t e = set_ptr[q]; e < set_ptr[q + 1]; ++e)
@@ -2393,7 +2375,7 @@ struct Solver : ISolver {
     npairs = (int64_t)slot.size();
     const int K = pick_k(npairs);
     ensure_csr();
-    W.ensure(n, K, H.levels.size() > 1 && H.levels[0].two_product() ? H.levels[1].A.nrows : 0);
+    W.ensure(n, K, tail_rows());
     W.drop_graphs();  // captured chunks hold the ground-set buffers of an earlier call
     if (stats) stats->batch = K;
     const Csr<T>& A = cg_matrix();
@@ -2454,15 +2436,7 @@ struct Solver : ISolver {
                                            0, st, (const int*)dptr<int>(dgp), (const int*)dptr<int>(dgi), W.rhs(),
                                            (T*)nullptr, (const int*)nullptr));
       CS_HIP(hipStreamSynchronize(st));  // the host lists are reused by the next batch
-      PcgBatchResult r;
-      {
-        PcgParams pp = pcg_params(K);
-        pp.need_x = true;
-        pp.gptr = dptr<int>(dgp);
-        pp.gidx = dptr<int>(dgi);
-        pp.gtotal = (int)gi.size();
-        CS_DISPATCH_K(K, r = (pcg_solve<T, TP, KK>(A, H, W, pp, ncols, st, dia_ptr())));
-      }
+      PcgBatchResult r = run_masked_batch_k(K, ncols, dgp, dgi, (int)gi.size());
       accumulate(stats, r, ncols);
       hipLaunchKernelGGL((subtract_kernel<T>), dim3(grid_for(n * K)), dim3(256), 0, st, (int64_t)n * K, dptr<T>(volt),
                          (const T*)dptr<T>(W.x));
@@ -2482,7 +2456,7 @@ struct Solver : ISolver {
         res_all[slot[(size_t)(p0 + c)]] = e > 0 ? 1.0 / e : -1.0;
       }
     }
-    if (stats) stats->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    call.done();
   }
 
   template <class U>
@@ -2903,6 +2877,26 @@ using csgpu::g_last_error;
     return CSGPU_INTERNAL;                           \
   }
 
+// What every solve entry point does around its call of the solver (inside CS_API_BEGIN / CS_API_END, after the argument
+// check): `stats` may be NULL and is zeroed, a call without columns is CSGPU_OK without touching the solver, and columns the
+// solver could not accept become CSGPU_NOT_CONVERGED with the reference's message (src/core.jl:639-641).
+template <class F>
+static int solve_call(int64_t ncols, csgpu_stats* stats, F body) {
+  csgpu_stats local;
+  csgpu_stats* s = stats ? stats : &local;
+  memset(s, 0, sizeof(*s));
+  if (ncols == 0) return CSGPU_OK;
+  body(s);
+  if (s->not_converged > 0) {
+    char buf[256];
+    snprintf(buf, sizeof(buf), "CG solver did not converge: relative residual %g exceeds tolerance 1e-4 (%d of %d right-hand sides)",
+             s->max_relres, s->not_converged, s->nrhs);
+    g_last_error = buf;
+    return CSGPU_NOT_CONVERGED;
+  }
+  return CSGPU_OK;
+}
+
 extern "C" {
 
 const char* csgpu_version(void) { return "csgpu 0.2 (gfx950)"; }
@@ -3150,17 +3144,7 @@ int csgpu_solve_raster(csgpu_handle* h, const void* source, void* curr_out, void
     g_last_error = "bad arguments";
     return CSGPU_BAD_ARGS;
   }
-  csgpu_stats local;
-  csgpu_stats* s = stats ? stats : &local;
-  h->solver->solve_raster(source, curr_out, volt_out, s);
-  if (s->not_converged > 0) {
-    char buf[256];
-    snprintf(buf, sizeof(buf), "CG solver did not converge: relative residual %g exceeds tolerance 1e-4 (%d of %d right-hand sides)",
-             s->max_relres, s->not_converged, s->nrhs);
-    g_last_error = buf;
-    return CSGPU_NOT_CONVERGED;
-  }
-  return CSGPU_OK;
+  return solve_call(1, stats, [&](csgpu_stats* s) { h->solver->solve_raster(source, curr_out, volt_out, s); });
   CS_API_END
 }
 
@@ -3217,19 +3201,9 @@ int csgpu_solve_pairs(csgpu_handle* h, const int64_t* src, const int64_t* dst, i
     g_last_error = "bad arguments";
     return CSGPU_BAD_ARGS;
   }
-  csgpu_stats local;
-  csgpu_stats* s = stats ? stats : &local;
-  memset(s, 0, sizeof(*s));
-  if (npairs == 0) return CSGPU_OK;
-  h->solver->solve_pairs(src, dst, npairs, volt_out, gather_idx, ngather, gathered_out, resist_out, s);
-  if (s->not_converged > 0) {
-    char buf[256];
-    snprintf(buf, sizeof(buf), "CG solver did not converge: relative residual %g exceeds tolerance 1e-4 (%d of %d right-hand sides)",
-             s->max_relres, s->not_converged, s->nrhs);
-    g_last_error = buf;
-    return CSGPU_NOT_CONVERGED;
-  }
-  return CSGPU_OK;
+  return solve_call(npairs, stats, [&](csgpu_stats* s) {
+    h->solver->solve_pairs(src, dst, npairs, volt_out, gather_idx, ngather, gathered_out, resist_out, s);
+  });
   CS_API_END
 }
 
@@ -3241,20 +3215,10 @@ int csgpu_solve_pairs_currents(csgpu_handle* h, const int64_t* src, const int64_
     g_last_error = "bad arguments";
     return CSGPU_BAD_ARGS;
   }
-  csgpu_stats local;
-  csgpu_stats* s = stats ? stats : &local;
-  memset(s, 0, sizeof(*s));
-  if (npairs == 0) return CSGPU_OK;
-  h->solver->solve_pairs(src, dst, npairs, volt_out, nullptr, 0, nullptr, resist_out, s, weights, curr_out, cum_curr_inout,
-                         max_curr_inout, branch_out);
-  if (s->not_converged > 0) {
-    char buf[256];
-    snprintf(buf, sizeof(buf), "CG solver did not converge: relative residual %g exceeds tolerance 1e-4 (%d of %d right-hand sides)",
-             s->max_relres, s->not_converged, s->nrhs);
-    g_last_error = buf;
-    return CSGPU_NOT_CONVERGED;
-  }
-  return CSGPU_OK;
+  return solve_call(npairs, stats, [&](csgpu_stats* s) {
+    h->solver->solve_pairs(src, dst, npairs, volt_out, nullptr, 0, nullptr, resist_out, s, weights, curr_out, cum_curr_inout,
+                           max_curr_inout, branch_out);
+  });
   CS_API_END
 }
 
@@ -3264,19 +3228,7 @@ int csgpu_solve_rhs(csgpu_handle* h, const void* rhs, int64_t nrhs, void* x_out,
     g_last_error = "bad arguments";
     return CSGPU_BAD_ARGS;
   }
-  csgpu_stats local;
-  csgpu_stats* s = stats ? stats : &local;
-  memset(s, 0, sizeof(*s));
-  if (nrhs == 0) return CSGPU_OK;
-  h->solver->solve_rhs(rhs, nrhs, x_out, s);
-  if (s->not_converged > 0) {
-    char buf[256];
-    snprintf(buf, sizeof(buf), "CG solver did not converge: relative residual %g exceeds tolerance 1e-4 (%d of %d right-hand sides)",
-             s->max_relres, s->not_converged, s->nrhs);
-    g_last_error = buf;
-    return CSGPU_NOT_CONVERGED;
-  }
-  return CSGPU_OK;
+  return solve_call(nrhs, stats, [&](csgpu_stats* s) { h->solver->solve_rhs(rhs, nrhs, x_out, s); });
   CS_API_END
 }
 
@@ -3288,37 +3240,15 @@ int csgpu_solve_region_pairs(csgpu_handle* h, const int64_t* set_ptr, const int6
     g_last_error = "bad arguments";
     return CSGPU_BAD_ARGS;
   }
-  csgpu_stats local;
-  csgpu_stats* s = stats ? stats : &local;
-  memset(s, 0, sizeof(*s));
-  if (npairs == 0) return CSGPU_OK;
-  h->solver->solve_region_pairs(set_ptr, set_nodes, nsets, src_set, dst_set, npairs, resistances, s);
-  if (s->not_converged > 0) {
-    char buf[256];
-    snprintf(buf, sizeof(buf), "CG solver did not converge: relative residual %g exceeds tolerance 1e-4 (%d of %d right-hand sides)",
-             s->max_relres, s->not_converged, s->nrhs);
-    g_last_error = buf;
-    return CSGPU_NOT_CONVERGED;
-  }
-  return CSGPU_OK;
+  return solve_call(npairs, stats, [&](csgpu_stats* s) {
+    h->solver->solve_region_pairs(set_ptr, set_nodes, nsets, src_set, dst_set, npairs, resistances, s);
+  });
   CS_API_END
 }
 
 static int grounded_call(csgpu_handle* h, const csgpu::GroundedJob& job, int64_t nrhs, csgpu_stats* stats) {
   CS_API_BEGIN
-  csgpu_stats local;
-  csgpu_stats* s = stats ? stats : &local;
-  memset(s, 0, sizeof(*s));
-  if (nrhs == 0) return CSGPU_OK;
-  h->solver->solve_grounded(job, nrhs, s);
-  if (s->not_converged > 0) {
-    char buf[256];
-    snprintf(buf, sizeof(buf), "CG solver did not converge: relative residual %g exceeds tolerance 1e-4 (%d of %d right-hand sides)",
-             s->max_relres, s->not_converged, s->nrhs);
-    g_last_error = buf;
-    return CSGPU_NOT_CONVERGED;
-  }
-  return CSGPU_OK;
+  return solve_call(nrhs, stats, [&](csgpu_stats* s) { h->solver->solve_grounded(job, nrhs, s); });
   CS_API_END
 }
 
@@ -3512,31 +3442,65 @@ int multi_build(const csgpu_opts* opts, const int32_t* devices, int ndevices, in
   return CSGPU_OK;
 }
 
+// THE merge of one csgpu_stats into another (DESIGN.md section 6 states the rules). `concurrent` is the one real difference:
+// calls that ran one after the other on a device add their device time and the last one's per-launch figures stand; devices
+// that ran side by side take the maximum of both. nrhs and solve_ms belong to the whole call and are set by the caller.
+// (stream_slots: 0 in every multi call that asks for a map -- map calls never stream -- and in csgpu_multi_solve_pairs,
+// whose chunks never exceed one batch; a csgpu_multi_solve_pairs_currents call without either map is a plain resistance
+// call per device and may stream, its slots are then reported.)
+void merge_stats(csgpu_stats& s, const csgpu_stats& a, bool concurrent) {
+  s.total_iters += a.total_iters;
+  s.not_converged += a.not_converged;
+  s.cg_spmv_ms += a.cg_spmv_ms;
+  s.cg_spmv_calls += a.cg_spmv_calls;
+  s.graph_launches += a.graph_launches;
+  s.polished_batches += a.polished_batches;
+  s.resid_ms += a.resid_ms;
+  s.resid_calls += a.resid_calls;
+  s.stream_slots += a.stream_slots;
+  s.max_iters = std::max(s.max_iters, a.max_iters);
+  s.max_relres = std::max(s.max_relres, a.max_relres);
+  s.batch = std::max(s.batch, a.batch);
+  s.lattice_maps = std::max(s.lattice_maps, a.lattice_maps);
+  s.device_ms = concurrent ? std::max(s.device_ms, a.device_ms) : s.device_ms + a.device_ms;
+  s.cg_spmv_bytes = concurrent ? std::max(s.cg_spmv_bytes, a.cg_spmv_bytes) : a.cg_spmv_bytes;
+  s.resid_bytes = concurrent ? std::max(s.resid_bytes, a.resid_bytes) : a.resid_bytes;
+  s.resid_fused = concurrent ? std::max(s.resid_fused, a.resid_fused) : a.resid_fused;
+}
+
+// what the worker of one device slot leaves behind
+struct MultiSlot {
+  int code = CSGPU_OK;
+  std::string msg;        // csgpu_last_error() of the worker's thread when code != CSGPU_OK
+  csgpu_stats st = {};
+  std::vector<char> cum, mx;  // the slot's cumulative / maximum node-current vectors (empty: none)
+};
+
 // the per-device cumulative / maximum node-current vectors of a job combined into the caller's arrays in slot order (sum /
 // max: deterministic), the index range split over host threads
-void multi_combine_maps(size_t nd, int64_t n, size_t vb, const std::vector<std::vector<char>>& cum,
-                        const std::vector<std::vector<char>>& mx, void* cum_curr_inout, void* max_curr_inout) {
+void multi_combine_maps(const std::vector<MultiSlot>& slots, int64_t n, size_t vb, void* cum_curr_inout, void* max_curr_inout) {
+  const size_t nd = slots.size();
   auto combine = [&](int64_t lo, int64_t hi) {
     for (size_t i = 0; i < nd; ++i) {
-      if (cum_curr_inout && !cum[i].empty()) {
+      if (cum_curr_inout && !slots[i].cum.empty()) {
         if (vb == 8) {
           double* o = (double*)cum_curr_inout;
-          const double* a = (const double*)cum[i].data();
+          const double* a = (const double*)slots[i].cum.data();
           for (int64_t k = lo; k < hi; ++k) o[k] += a[k];
         } else {
           float* o = (float*)cum_curr_inout;
-          const float* a = (const float*)cum[i].data();
+          const float* a = (const float*)slots[i].cum.data();
           for (int64_t k = lo; k < hi; ++k) o[k] += a[k];
         }
       }
-      if (max_curr_inout && !mx[i].empty()) {
+      if (max_curr_inout && !slots[i].mx.empty()) {
         if (vb == 8) {
           double* o = (double*)max_curr_inout;
-          const double* a = (const double*)mx[i].data();
+          const double* a = (const double*)slots[i].mx.data();
           for (int64_t k = lo; k < hi; ++k) o[k] = a[k] > o[k] ? a[k] : o[k];
         } else {
           float* o = (float*)max_curr_inout;
-          const float* a = (const float*)mx[i].data();
+          const float* a = (const float*)slots[i].mx.data();
           for (int64_t k = lo; k < hi; ++k) o[k] = a[k] > o[k] ? a[k] : o[k];
         }
       }
@@ -3547,6 +3511,53 @@ void multi_combine_maps(size_t nd, int64_t n, size_t vb, const std::vector<std::
   for (int t = 1; t < nt; ++t) ct.emplace_back(combine, n * t / nt, n * (t + 1) / nt);
   combine(0, n / nt);
   for (auto& t : ct) t.join();
+}
+
+// One call of a device set: worker(slot, MultiSlot&, n) runs on one host thread per slot (slot 0 on the caller's) and leaves
+// its code, message, stats and maps in its MultiSlot. The stats are merged; the first hard error in slot order wins over
+// CSGPU_NOT_CONVERGED, which wins over CSGPU_OK; unless a device failed hard the slots' maps (vectors of n values) are
+// combined into the caller's. node_maps: the call can carry such maps and n, the handles' node count, is looked up (else 0).
+template <class W>
+int multi_fan_out(csgpu_multi* m, int64_t nrhs, csgpu_stats* stats, bool node_maps, void* cum_curr_inout,
+                  void* max_curr_inout, W worker) {
+  csgpu_stats local;
+  csgpu_stats* s = stats ? stats : &local;
+  memset(s, 0, sizeof(*s));
+  const size_t nd = m->handles.size();
+  std::fill(m->busy_s.begin(), m->busy_s.end(), 0.0);
+  std::fill(m->pairs_done.begin(), m->pairs_done.end(), 0);
+  if (nrhs == 0) return CSGPU_OK;
+  auto t0 = std::chrono::steady_clock::now();
+  int64_t n = 0;
+  if (node_maps) {
+    csgpu_info info;
+    int rc = csgpu_get_info(m->handles[0], &info);
+    if (rc) return rc;
+    n = info.n;
+  }
+  std::vector<MultiSlot> slots(nd);
+  auto timed = [&](size_t slot) {
+    auto w0 = std::chrono::steady_clock::now();
+    worker(slot, slots[slot], n);
+    m->busy_s[slot] = std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
+  };
+  std::vector<std::thread> th;
+  for (size_t i = 1; i < nd; ++i) th.emplace_back(timed, i);
+  timed(0);
+  for (auto& t : th) t.join();
+  s->nrhs = (int)nrhs;
+  int rc_out = CSGPU_OK;
+  for (size_t i = 0; i < nd; ++i) {
+    merge_stats(*s, slots[i].st, true);
+    if (slots[i].code != CSGPU_OK && (rc_out == CSGPU_OK || rc_out == CSGPU_NOT_CONVERGED)) {
+      rc_out = slots[i].code;
+      g_last_error = "device " + std::to_string(m->devices[i]) + ": " + slots[i].msg;
+    }
+  }
+  if ((rc_out == CSGPU_OK || rc_out == CSGPU_NOT_CONVERGED) && (cum_curr_inout || max_curr_inout))
+    multi_combine_maps(slots, n, (size_t)m->val_bytes, cum_curr_inout, max_curr_inout);
+  s->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return rc_out;
 }
 
 }  // namespace
@@ -3589,89 +3600,31 @@ int csgpu_multi_solve_pairs(csgpu_multi* m, const int64_t* src, const int64_t* d
     g_last_error = "bad arguments";
     return CSGPU_BAD_ARGS;
   }
-  csgpu_stats local;
-  csgpu_stats* s = stats ? stats : &local;
-  memset(s, 0, sizeof(*s));
   const size_t nd = m->handles.size();
-  std::fill(m->busy_s.begin(), m->busy_s.end(), 0.0);
-  std::fill(m->pairs_done.begin(), m->pairs_done.end(), 0);
-  if (npairs == 0) return CSGPU_OK;
-  auto t0 = std::chrono::steady_clock::now();
   // chunk = one batch; fewer batches than devices: shrink the chunk so that every device gets one
   int64_t chunk = m->batch;
   if ((npairs + chunk - 1) / chunk < (int64_t)nd) chunk = std::max<int64_t>(1, (npairs + (int64_t)nd - 1) / (int64_t)nd);
   const int64_t nchunks = (npairs + chunk - 1) / chunk;
   std::atomic<int64_t> next{0};
-  std::vector<int> codes(nd, CSGPU_OK);
-  std::vector<std::string> msgs(nd);
-  std::vector<csgpu_stats> st(nd);
-  for (auto& x : st) memset(&x, 0, sizeof(x));
   const size_t vb = (size_t)m->val_bytes;
-  auto worker = [&](size_t slot) {
-    auto w0 = std::chrono::steady_clock::now();
+  return multi_fan_out(m, npairs, stats, false, nullptr, nullptr, [&](size_t slot, MultiSlot& S, int64_t) {
     for (;;) {
       const int64_t c = next.fetch_add(1);
       if (c >= nchunks) break;
       const int64_t off = c * chunk, cnt = std::min(chunk, npairs - off);
-      csgpu_stats cs;
+      csgpu_stats cs = {};
       const int rc = csgpu_solve_pairs(m->handles[slot], src + off, dst + off, cnt, nullptr, gather_idx, ngather,
                                        gathered_out ? (char*)gathered_out + (size_t)off * ngather * vb : nullptr,
                                        resist_out ? (char*)resist_out + (size_t)off * vb : nullptr, &cs);
-      st[slot].total_iters += cs.total_iters;
-      st[slot].max_iters = std::max(st[slot].max_iters, cs.max_iters);
-      st[slot].max_relres = std::max(st[slot].max_relres, cs.max_relres);
-      st[slot].device_ms += cs.device_ms;
-      st[slot].cg_spmv_ms += cs.cg_spmv_ms;
-      st[slot].cg_spmv_calls += cs.cg_spmv_calls;
-      st[slot].not_converged += cs.not_converged;
-      st[slot].graph_launches += cs.graph_launches;
-      st[slot].polished_batches += cs.polished_batches;
-      st[slot].cg_spmv_bytes = cs.cg_spmv_bytes;
-      st[slot].resid_ms += cs.resid_ms;
-      st[slot].resid_calls += cs.resid_calls;
-      st[slot].resid_bytes = cs.resid_bytes;
-      st[slot].resid_fused = cs.resid_fused;
-      st[slot].lattice_maps = std::max(st[slot].lattice_maps, cs.lattice_maps);
-      st[slot].batch = std::max(st[slot].batch, cs.batch);
+      merge_stats(S.st, cs, false);
       m->pairs_done[slot] += cnt;
-      if (rc != CSGPU_OK && codes[slot] == CSGPU_OK) {
-        codes[slot] = rc;
-        msgs[slot] = csgpu_last_error();
+      if (rc != CSGPU_OK && S.code == CSGPU_OK) {
+        S.code = rc;
+        S.msg = csgpu_last_error();
         if (rc != CSGPU_NOT_CONVERGED) break;  // hard error: stop this device; a non-converged chunk is only reported
       }
     }
-    m->busy_s[slot] = std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
-  };
-  std::vector<std::thread> th;
-  for (size_t i = 1; i < nd; ++i) th.emplace_back(worker, i);
-  worker(0);
-  for (auto& t : th) t.join();
-  s->nrhs = (int)npairs;
-  int rc_out = CSGPU_OK;
-  for (size_t i = 0; i < nd; ++i) {
-    s->total_iters += st[i].total_iters;
-    s->max_iters = std::max(s->max_iters, st[i].max_iters);
-    s->max_relres = std::max(s->max_relres, st[i].max_relres);
-    s->device_ms = std::max(s->device_ms, st[i].device_ms);
-    s->cg_spmv_ms += st[i].cg_spmv_ms;
-    s->cg_spmv_calls += st[i].cg_spmv_calls;
-    s->not_converged += st[i].not_converged;
-    s->graph_launches += st[i].graph_launches;
-    s->polished_batches += st[i].polished_batches;
-    s->cg_spmv_bytes = std::max(s->cg_spmv_bytes, st[i].cg_spmv_bytes);
-    s->resid_ms += st[i].resid_ms;
-    s->resid_calls += st[i].resid_calls;
-    s->resid_bytes = std::max(s->resid_bytes, st[i].resid_bytes);
-    s->resid_fused = std::max(s->resid_fused, st[i].resid_fused);
-    s->lattice_maps = std::max(s->lattice_maps, st[i].lattice_maps);
-    s->batch = std::max(s->batch, st[i].batch);
-    if (codes[i] != CSGPU_OK && (rc_out == CSGPU_OK || rc_out == CSGPU_NOT_CONVERGED)) {
-      rc_out = codes[i];
-      g_last_error = "device " + std::to_string(m->devices[i]) + ": " + msgs[i];
-    }
-  }
-  s->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return rc_out;
+  });
   CS_API_END
 }
 
@@ -3688,86 +3641,34 @@ int csgpu_multi_solve_pairs_currents(csgpu_multi* m, const int64_t* src, const i
     g_last_error = "bad arguments";
     return CSGPU_BAD_ARGS;
   }
-  csgpu_stats local;
-  csgpu_stats* s = stats ? stats : &local;
-  memset(s, 0, sizeof(*s));
-  const size_t nd = m->handles.size();
-  std::fill(m->busy_s.begin(), m->busy_s.end(), 0.0);
-  std::fill(m->pairs_done.begin(), m->pairs_done.end(), 0);
-  if (npairs == 0) return CSGPU_OK;
-  auto t0 = std::chrono::steady_clock::now();
-  csgpu_info info;
-  int rc = csgpu_get_info(m->handles[0], &info);
-  if (rc) return rc;
-  const int64_t n = info.n;
+  const int64_t nd = (int64_t)m->handles.size();
   const size_t vb = (size_t)m->val_bytes;
   int64_t chunk = m->batch;
-  if ((npairs + chunk - 1) / chunk < (int64_t)nd) chunk = std::max<int64_t>(1, (npairs + (int64_t)nd - 1) / (int64_t)nd);
-  // the pairs of every slot, in the caller's order
-  std::vector<std::vector<int64_t>> idx(nd);
-  for (int64_t p = 0; p < npairs; ++p) idx[(size_t)((p / chunk) % (int64_t)nd)].push_back(p);
-  std::vector<int> codes(nd, CSGPU_OK);
-  std::vector<std::string> msgs(nd);
-  std::vector<csgpu_stats> st(nd);
-  for (auto& x : st) memset(&x, 0, sizeof(x));
-  std::vector<std::vector<char>> cum(nd), mx(nd);
-  auto worker = [&](size_t slot) {
-    auto w0 = std::chrono::steady_clock::now();
-    const std::vector<int64_t>& mine = idx[slot];
+  if ((npairs + chunk - 1) / chunk < nd) chunk = std::max<int64_t>(1, (npairs + nd - 1) / nd);
+  return multi_fan_out(m, npairs, stats, true, cum_curr_inout, max_curr_inout, [&](size_t slot, MultiSlot& S, int64_t n) {
+    std::vector<int64_t> mine;  // the pairs of this slot, in the caller's order
+    for (int64_t p = 0; p < npairs; ++p)
+      if ((p / chunk) % nd == (int64_t)slot) mine.push_back(p);
     const int64_t cnt = (int64_t)mine.size();
-    if (cnt > 0) {
-      std::vector<int64_t> s_(cnt), d_(cnt);
-      std::vector<int32_t> w_(cnt);
-      for (int64_t k = 0; k < cnt; ++k) {
-        s_[k] = src[mine[k]];
-        d_[k] = dst[mine[k]];
-        w_[k] = weights ? weights[mine[k]] : 1;
-      }
-      if (cum_curr_inout) cum[slot].assign((size_t)n * vb, 0);
-      if (max_curr_inout) mx[slot].assign((size_t)n * vb, 0);
-      std::vector<char> res((size_t)cnt * vb);
-      codes[slot] = csgpu_solve_pairs_currents(m->handles[slot], s_.data(), d_.data(), cnt, w_.data(), nullptr, nullptr,
-                                               cum_curr_inout ? cum[slot].data() : nullptr,
-                                               max_curr_inout ? mx[slot].data() : nullptr, nullptr, res.data(), &st[slot]);
-      if (codes[slot]) msgs[slot] = csgpu_last_error();
-      if (resist_out && (codes[slot] == CSGPU_OK || codes[slot] == CSGPU_NOT_CONVERGED))
-        for (int64_t k = 0; k < cnt; ++k) memcpy((char*)resist_out + (size_t)mine[k] * vb, res.data() + (size_t)k * vb, vb);
-      m->pairs_done[slot] = cnt;
+    if (cnt == 0) return;
+    std::vector<int64_t> s_(cnt), d_(cnt);
+    std::vector<int32_t> w_(cnt);
+    for (int64_t k = 0; k < cnt; ++k) {
+      s_[k] = src[mine[k]];
+      d_[k] = dst[mine[k]];
+      w_[k] = weights ? weights[mine[k]] : 1;
     }
-    m->busy_s[slot] = std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
-  };
-  std::vector<std::thread> th;
-  for (size_t i = 1; i < nd; ++i) th.emplace_back(worker, i);
-  worker(0);
-  for (auto& t : th) t.join();
-  s->nrhs = (int)npairs;
-  int rc_out = CSGPU_OK;
-  for (size_t i = 0; i < nd; ++i) {
-    s->total_iters += st[i].total_iters;
-    s->max_iters = std::max(s->max_iters, st[i].max_iters);
-    s->max_relres = std::max(s->max_relres, st[i].max_relres);
-    s->device_ms = std::max(s->device_ms, st[i].device_ms);
-    s->cg_spmv_ms += st[i].cg_spmv_ms;
-    s->cg_spmv_calls += st[i].cg_spmv_calls;
-    s->not_converged += st[i].not_converged;
-    s->graph_launches += st[i].graph_launches;
-    s->polished_batches += st[i].polished_batches;
-    s->cg_spmv_bytes = std::max(s->cg_spmv_bytes, st[i].cg_spmv_bytes);
-    s->resid_ms += st[i].resid_ms;
-    s->resid_calls += st[i].resid_calls;
-    s->resid_bytes = std::max(s->resid_bytes, st[i].resid_bytes);
-    s->resid_fused = std::max(s->resid_fused, st[i].resid_fused);
-    s->lattice_maps = std::max(s->lattice_maps, st[i].lattice_maps);
-    s->batch = std::max(s->batch, st[i].batch);
-    if (codes[i] != CSGPU_OK && (rc_out == CSGPU_OK || rc_out == CSGPU_NOT_CONVERGED)) {
-      rc_out = codes[i];
-      g_last_error = "device " + std::to_string(m->devices[i]) + ": " + msgs[i];
-    }
-  }
-  if (rc_out == CSGPU_OK || rc_out == CSGPU_NOT_CONVERGED)
-    multi_combine_maps(nd, n, vb, cum, mx, cum_curr_inout, max_curr_inout);
-  s->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return rc_out;
+    if (cum_curr_inout) S.cum.assign((size_t)n * vb, 0);
+    if (max_curr_inout) S.mx.assign((size_t)n * vb, 0);
+    std::vector<char> res((size_t)cnt * vb);
+    S.code = csgpu_solve_pairs_currents(m->handles[slot], s_.data(), d_.data(), cnt, w_.data(), nullptr, nullptr,
+                                        cum_curr_inout ? S.cum.data() : nullptr, max_curr_inout ? S.mx.data() : nullptr,
+                                        nullptr, res.data(), &S.st);
+    if (S.code) S.msg = csgpu_last_error();
+    if (resist_out && (S.code == CSGPU_OK || S.code == CSGPU_NOT_CONVERGED))
+      for (int64_t k = 0; k < cnt; ++k) memcpy((char*)resist_out + (size_t)mine[k] * vb, res.data() + (size_t)k * vb, vb);
+    m->pairs_done[slot] = cnt;
+  });
   CS_API_END
 }
 
@@ -3782,77 +3683,26 @@ namespace {
 // job_of(lo, hi) returns the GroundedJob of that range without the cumulative / maximum pointers.
 template <class F>
 int multi_grounded(csgpu_multi* m, int64_t nrhs, void* cum_curr_inout, void* max_curr_inout, csgpu_stats* stats, F job_of) {
-  csgpu_stats local;
-  csgpu_stats* s = stats ? stats : &local;
-  memset(s, 0, sizeof(*s));
-  const size_t nd = m->handles.size();
-  std::fill(m->busy_s.begin(), m->busy_s.end(), 0.0);
-  std::fill(m->pairs_done.begin(), m->pairs_done.end(), 0);
-  if (nrhs == 0) return CSGPU_OK;
-  auto t0 = std::chrono::steady_clock::now();
-  csgpu_info info;
-  int rc = csgpu_get_info(m->handles[0], &info);
-  if (rc) return rc;
-  const int64_t n = info.n;
+  const int64_t nd = (int64_t)m->handles.size();
   const size_t vb = (size_t)m->val_bytes;
-  std::vector<int> codes(nd, CSGPU_OK);
-  std::vector<std::string> msgs(nd);
-  std::vector<csgpu_stats> st(nd);
-  for (auto& x : st) memset(&x, 0, sizeof(x));
-  std::vector<std::vector<char>> cum(nd), mx(nd);
-  auto worker = [&](size_t slot) {
-    auto w0 = std::chrono::steady_clock::now();
-    const int64_t base = nrhs / (int64_t)nd, rem = nrhs % (int64_t)nd;
+  return multi_fan_out(m, nrhs, stats, true, cum_curr_inout, max_curr_inout, [&](size_t slot, MultiSlot& S, int64_t n) {
+    const int64_t base = nrhs / nd, rem = nrhs % nd;
     const int64_t lo = (int64_t)slot * base + std::min<int64_t>((int64_t)slot, rem);
     const int64_t hi = lo + base + ((int64_t)slot < rem ? 1 : 0);
-    if (hi > lo) {
-      csgpu::GroundedJob job = job_of(lo, hi);
-      if (cum_curr_inout) {
-        cum[slot].assign((size_t)n * vb, 0);
-        job.cum_inout = cum[slot].data();
-      }
-      if (max_curr_inout) {
-        mx[slot].assign((size_t)n * vb, 0);
-        job.max_inout = mx[slot].data();
-      }
-      codes[slot] = grounded_call(m->handles[slot], job, hi - lo, &st[slot]);
-      if (codes[slot]) msgs[slot] = csgpu_last_error();
-      m->pairs_done[slot] = hi - lo;
+    if (hi == lo) return;
+    csgpu::GroundedJob job = job_of(lo, hi);
+    if (cum_curr_inout) {
+      S.cum.assign((size_t)n * vb, 0);
+      job.cum_inout = S.cum.data();
     }
-    m->busy_s[slot] = std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
-  };
-  std::vector<std::thread> th;
-  for (size_t i = 1; i < nd; ++i) th.emplace_back(worker, i);
-  worker(0);
-  for (auto& t : th) t.join();
-  s->nrhs = (int)nrhs;
-  int rc_out = CSGPU_OK;
-  for (size_t i = 0; i < nd; ++i) {
-    s->total_iters += st[i].total_iters;
-    s->max_iters = std::max(s->max_iters, st[i].max_iters);
-    s->max_relres = std::max(s->max_relres, st[i].max_relres);
-    s->device_ms = std::max(s->device_ms, st[i].device_ms);
-    s->cg_spmv_ms += st[i].cg_spmv_ms;
-    s->cg_spmv_calls += st[i].cg_spmv_calls;
-    s->not_converged += st[i].not_converged;
-    s->graph_launches += st[i].graph_launches;
-    s->polished_batches += st[i].polished_batches;
-    s->cg_spmv_bytes = std::max(s->cg_spmv_bytes, st[i].cg_spmv_bytes);
-    s->resid_ms += st[i].resid_ms;
-    s->resid_calls += st[i].resid_calls;
-    s->resid_bytes = std::max(s->resid_bytes, st[i].resid_bytes);
-    s->resid_fused = std::max(s->resid_fused, st[i].resid_fused);
-    s->lattice_maps = std::max(s->lattice_maps, st[i].lattice_maps);
-    s->batch = std::max(s->batch, st[i].batch);
-    if (codes[i] != CSGPU_OK && (rc_out == CSGPU_OK || rc_out == CSGPU_NOT_CONVERGED)) {
-      rc_out = codes[i];
-      g_last_error = "device " + std::to_string(m->devices[i]) + ": " + msgs[i];
+    if (max_curr_inout) {
+      S.mx.assign((size_t)n * vb, 0);
+      job.max_inout = S.mx.data();
     }
-  }
-  if ((rc_out == CSGPU_OK || rc_out == CSGPU_NOT_CONVERGED) && (cum_curr_inout || max_curr_inout))
-    multi_combine_maps(nd, n, vb, cum, mx, cum_curr_inout, max_curr_inout);
-  s->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return rc_out;
+    S.code = grounded_call(m->handles[slot], job, hi - lo, &S.st);
+    if (S.code) S.msg = csgpu_last_error();
+    m->pairs_done[slot] = hi - lo;
+  });
 }
 
 }  // namespace
