@@ -8,6 +8,7 @@
 
 #include "currents.h"
 #include "lattice_currents.h"
+#include "lattice_components.h"
 #include "pairs.h"
 #include "pcg.h"
 #include "raster.h"
@@ -320,7 +321,8 @@ struct Solver : ISolver {
   bool translated() const { return cellspace || reordered; }
   // Rasters set up through the lattice pipeline (lattice_setup.h) hold NO CSR form of the fine-level matrix: resistance-
   // only pair solves never touch one. Entry points that do (current maps, explicit residual checks of full solutions,
-  // region pairs, components, the product hooks) build it from the lattice form on first use (ensure_csr).
+  // region pairs, components, the product hooks) build it from the lattice form on first use (ensure_csr) -- unless
+  // csgpu_opts.lattice_maps serves the call from the lattice form (lattice_form_path).
   bool csr_ready = true;
   // Test hooks only: level 0 rebuilt by the CSR pipeline of amg_setup.h (A, P, R, Q, Q^T, [S Q] in CSR) for a handle
   // whose level 0 came from the lattice pipeline -- csgpu_get_level_matrix / csgpu_level_spmv_host then compare the two
@@ -840,8 +842,11 @@ struct Solver : ISolver {
   // from the lattice form (lattice_currents.h, PcgParams::lattice_check) instead of the CSR form? Raster numbering only (the
   // device rows are monotone in the caller's nodes, so a branch's orientation is that of the device ids); branch currents are
   // indexed by the stored entries of a CSR matrix and stay there.
-  bool lattice_maps_path(bool want_branch) const {
-    if (!dia_ptr() || poly_proj || reordered || want_branch || kn.lattice_maps < 0) return false;
+  bool lattice_maps_path(bool want_branch) const { return !want_branch && lattice_form_path(); }
+  // The one rule of csgpu_opts.lattice_maps, for every call that can be served from the lattice form: those pair solves,
+  // csgpu_components (lattice_components.h) and csgpu_solve_rhs (whose only CSR reader is the explicit post-check).
+  bool lattice_form_path() const {
+    if (!dia_ptr() || poly_proj || reordered || kn.lattice_maps < 0) return false;
     if (kn.lattice_maps > 0) return true;
     return !csr_ready && nnz >= ((int64_t)1 << 31);  // default: only where ensure_csr() would refuse
   }
@@ -1580,6 +1585,11 @@ struct Solver : ISolver {
       ncomp = ncomp_api;
       return;
     }
+    if (lattice_form_path()) {  // (csgpu_opts.lattice_maps: the hooking pass reads the lattice form, no CSR form is built)
+      comp_label.alloc((size_t)n * sizeof(int));
+      ncomp = dia_connected_components<T>(dia, dptr<int>(comp_label), st);
+      return;
+    }
     ensure_csr();
     const Csr<T>& A = cg_matrix();
     comp_label.alloc((size_t)n * sizeof(int));
@@ -2134,11 +2144,15 @@ struct Solver : ISolver {
     if (poly_proj) return poly_fallback().solve_rhs(rhs, nrhs, x_out, stats);
     CallScope call(*this, stats);
     const int K = pick_k(nrhs);
-    ensure_csr();
+    // The PCG iteration of such a handle runs from the lattice form; the explicit post-check is the one CSR reader and has a
+    // lattice twin (PcgParams::lattice_check), so on the lattice path (csgpu_opts.lattice_maps) no CSR form is built.
+    const bool lattice = lattice_form_path();
+    if (!lattice) ensure_csr();
     W.ensure(n, K, tail_rows());
     if (stats) {
       stats->nrhs = (int)nrhs;
       stats->batch = K;
+      stats->lattice_maps = lattice ? 1 : 0;
     }
     DBuf stage((size_t)n * K * sizeof(T));
     for (int64_t p0 = 0; p0 < nrhs; p0 += K) {
@@ -2146,7 +2160,8 @@ struct Solver : ISolver {
       upload_cols((const T*)rhs + (size_t)p0 * n_api, ncols, dptr<T>(stage));
       CS_DISPATCH_K(K, hipLaunchKernelGGL((interleave_kernel<T, KK>), dim3(grid_for(n * K)), dim3(256), 0, st, n,
                                            (const T*)dptr<T>(stage), ncols, W.rhs()));
-      PcgBatchResult r = run_batch_k(K, ncols);
+      PcgBatchResult r = run_batch_k(K, ncols, true, nullptr, nullptr, nullptr, lattice);
+      CS_REQUIRE(!lattice || r.lattice_check == 1, CSGPU_INTERNAL, "lattice-path solve_rhs whose post-check left the lattice form");
       accumulate(stats, r, ncols);
       CS_DISPATCH_K(K, hipLaunchKernelGGL((deinterleave_kernel<T, KK>), dim3(grid_for(n * ncols)), dim3(256), 0, st, n,
                                            (const T*)dptr<T>(W.x), ncols, dptr<T>(stage)));

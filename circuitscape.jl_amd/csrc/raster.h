@@ -283,16 +283,18 @@ __global__ __launch_bounds__(256) void cc_relabel_kernel(int n, const int* __res
   for (int u = blockIdx.x * 256 + threadIdx.x; u < n; u += gridDim.x * 256) label[u] = idx[f[u]];
 }
 
+// The rounds of hooking and pointer jumping, and the dense relabelling, of any form of the graph: hook(grid, f, changed)
+// launches one hooking pass over the edges (cc_hook_kernel here, dia_cc_hook_kernel of lattice_components.h).
 // label[u] = dense component index (components ordered by their smallest node id); returns the number of components.
-template <class T>
-inline int connected_components(int n, const int* rp, const int* ci, const T* va, int* label, hipStream_t st) {
+template <class Hook>
+inline int connected_components_rounds(int n, int* label, hipStream_t st, Hook hook) {
   if (n <= 0) return 0;
   DBuf f = dalloc<int>(n), flag = dalloc<int>((size_t)n + 1), changed = dalloc<int>(1);
   const int g = grid_for(n);
   hipLaunchKernelGGL(iota_kernel, dim3(g), dim3(256), 0, st, dptr<int>(f), (int64_t)n);
   for (int round = 0; round < 256; ++round) {
     CS_HIP(hipMemsetAsync(changed.p, 0, sizeof(int), st));
-    hipLaunchKernelGGL((cc_hook_kernel<T>), dim3(g), dim3(256), 0, st, n, rp, ci, va, dptr<int>(f), dptr<int>(changed));
+    hook(g, dptr<int>(f), dptr<int>(changed));
     if (read_int(dptr<int>(changed), st) == 0) break;
     for (int pass = 0; pass < 64; ++pass) {
       CS_HIP(hipMemsetAsync(changed.p, 0, sizeof(int), st));
@@ -308,6 +310,13 @@ inline int connected_components(int n, const int* rp, const int* ci, const T* va
   hipLaunchKernelGGL(cc_relabel_kernel, dim3(g), dim3(256), 0, st, n, dptr<int>(f), dptr<int>(flag), label);
   check_launch("connected components");
   return read_int(dptr<int>(total), st);
+}
+
+template <class T>
+inline int connected_components(int n, const int* rp, const int* ci, const T* va, int* label, hipStream_t st) {
+  return connected_components_rounds(n, label, st, [&](int g, int* f, int* changed) {
+    hipLaunchKernelGGL((cc_hook_kernel<T>), dim3(g), dim3(256), 0, st, n, rp, ci, va, f, changed);
+  });
 }
 
 // nzval .+= eps(T) * norm(nzval)   (src/core.jl:161); norm2 partials come from dot_kernel<T,1,false>

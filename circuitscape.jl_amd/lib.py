@@ -538,6 +538,13 @@ class MultiHandle:
         _check(lib().csgpu_get_permutation(lib().csgpu_multi_handle(self._p, slot), perm.ctypes.data))
         return perm
 
+    def components(self, slot=0):
+        """Handle.components() of the replica in device slot `slot` (csgpu_components on csgpu_multi_handle)."""
+        lab = np.zeros(self.info(slot)["n"], dtype=np.int32)
+        nc = ctypes.c_int64(0)
+        _check(lib().csgpu_components(lib().csgpu_multi_handle(self._p, slot), lab.ctypes.data, ctypes.byref(nc)))
+        return lab, nc.value
+
     def solve_pairs(self, src, dst, gather=None):
         """As Handle.solve_pairs (no voltages). Returns (resistances, gathered or None, stats dict incl. the per-device
         busy seconds and pair counts of this call)."""

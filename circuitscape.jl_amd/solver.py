@@ -791,10 +791,13 @@ def raster_pairwise_on_device(cellmap, points_rc, solver, four_neighbors=False, 
                               stats=None, cum=None, polymap=None):
     """Pairwise mode for a raster with the whole graph layer on the device (scope row N4), short-circuit polygons
     included (`polymap`: cells of a polygon share one node, csgpu_raster_setup_poly):
-    csgpu_raster_setup numbers the valid cells, writes the CSR Laplacian in HBM and regularises it (core.jl:161),
+    csgpu_raster_setup numbers the valid cells, writes the regularised Laplacian (core.jl:161) in HBM -- in the lattice
+    form (five values per cell) where the raster takes the index-free pipeline, as a CSR matrix otherwise --,
     csgpu_components labels the connected components, and every solvable pair goes to csgpu_solve_pairs in ONE
     call on ONE handle (the Laplacian of all components is block diagonal; a pair's right-hand side lives in one
-    block). No n-sized array is built on the host except the node map it asks for.
+    block). No n-sized array is built on the host except the node map it asks for. On a lattice-form handle
+    csgpu_components builds the CSR form on first use by default; with HIPAMGSolver(opts={"lattice_maps": 1}) a run
+    never builds one, from the components through the resistances to the cumulative and maximum maps.
 
     points_rc: (rows, cols, ids), 1-based, unique ids. Returns the padded resistance matrix of
     single_ground_all_pairs (core.jl:130,294-299): -1 for pairs in different components or excluded, 0 on the

@@ -65,9 +65,11 @@
  *     scattered straight into the same lattice form (csgpu_get_info().host_blocks tells; status 4 with the reason when the
  *     matrix does not qualify). Pair solves on such a handle need no CSR form whatever they return: voltage maps,
  *     node-current, cumulative and maximum maps and explicit_check are computed from the lattice form
- *     (csgpu_opts.lattice_maps; csgpu_stats.lattice_maps = 1, csgpu_info.csr_built stays 0). The calls that still walk a CSR
- *     form -- csgpu_solve_rhs, csgpu_solve_grounded / _sources, csgpu_solve_raster, region pairs, csgpu_components, the
- *     product hooks, and every pair solve under lattice_maps = -1 -- return status 4 on a handle of that size.
+ *     (csgpu_opts.lattice_maps; csgpu_stats.lattice_maps = 1, csgpu_info.csr_built stays 0). So do csgpu_components (the
+ *     hooking pass reads the lattice form, csrc/lattice_components.h) and csgpu_solve_rhs (its explicit post-check is the
+ *     lattice one). The calls that still walk a CSR form -- csgpu_solve_grounded / _sources, csgpu_solve_raster, region
+ *     pairs, branch currents, the product hooks, and every call under lattice_maps = -1 -- return status 4 on a handle of
+ *     that size.
  *   - All calls are blocking; a handle is serialised internally (one caller at a time per handle).
  *   - Return value: 0 ok, 1 not converged (some right-hand side failed the reference's 1e-4 true-residual check,
  *     src/core.jl:640-641 -- the reference's only acceptance test: how the iteration stopped (rule met, itmax, breakdown of
@@ -270,7 +272,12 @@ typedef struct csgpu_opts {
                                  without polygons; not with csgpu_opts.reorder): 1 = the explicit residual check and the node
                                  currents are computed from the lattice form (csrc/lattice_currents.h) and no CSR form of the
                                  fine-level matrix is built or read -- every number returned equals the CSR path's bit for
-                                 bit, except max_relres, whose residual is summed in another order; -1 = never (a raster with
+                                 bit, except max_relres, whose residual is summed in another order; the same value serves
+                                 csgpu_components (labels and count equal to the CSR path's) and csgpu_solve_rhs (same
+                                 solution bit for bit) from the lattice form, so that a run from the components through the
+                                 resistances to the maps never builds a CSR form; csgpu_solve_grounded / _sources,
+                                 csgpu_solve_raster, region pairs and branch currents build and read it whatever the value;
+                                 -1 = never (a raster with
                                  2^31 stored entries then returns status 4 for these calls); 0 = library default: the CSR
                                  path wherever the handle can hold a CSR form, the lattice path where it cannot (nnz >= 2^31).
                                  csgpu_stats.lattice_maps tells which one a call took, csgpu_info.csr_built whether the
@@ -449,7 +456,10 @@ int csgpu_raster_nodemap(csgpu_handle* h, int32_t* nodemap_out, int64_t* nrows, 
 
 /* Connected components of the handle's graph (connected_components(SimpleGraph(G)), src/raster/pairwise.jl:233,
  * src/raster/advanced.jl:59), computed on the device: component_out[node] (n entries, may be NULL) = dense 0-based
- * component index, components ordered by their smallest node id; *ncomponents = their number. */
+ * component index, components ordered by their smallest node id; *ncomponents = their number. On a lattice-form handle
+ * the first call builds the CSR form of the matrix (status 4 with 2^31 stored entries or more under lattice_maps = -1)
+ * unless csgpu_opts.lattice_maps sends it to the lattice form (1, or 0 on a handle that cannot hold a CSR form): the same
+ * labels, no CSR form. Polygon handles answer from the merged graph, reordered handles with their set-up labels. */
 int csgpu_components(csgpu_handle* h, int32_t* component_out, int64_t* ncomponents);
 
 int csgpu_get_info(const csgpu_handle* h, csgpu_info* info);
@@ -480,7 +490,9 @@ int csgpu_solve_pairs_currents(csgpu_handle* h, const int64_t* src, const int64_
                                const int32_t* weights, void* volt_out, void* curr_out, void* cum_curr_inout,
                                void* max_curr_inout, void* branch_out, void* resist_out, csgpu_stats* stats);
 
-/* General right-hand sides: rhs and x_out are host column-major n x nrhs arrays of the handle's value type. */
+/* General right-hand sides: rhs and x_out are host column-major n x nrhs arrays of the handle's value type. The explicit
+ * post-check reads the CSR form of the matrix, or -- csgpu_opts.lattice_maps, as for csgpu_components -- the lattice form
+ * (csgpu_stats.lattice_maps = 1; x_out is the same bit for bit, max_relres is summed in another order). */
 int csgpu_solve_rhs(csgpu_handle* h, const void* rhs, int64_t nrhs, void* x_out, csgpu_stats* stats);
 
 /* Scope row N2 -- right-hand sides whose systems differ only in WHICH nodes are tied directly to ground, solved on ONE
